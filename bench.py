@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- prefilter+align throughput of the MI355X hot path on the BASELINE workload.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up the workload, warms up, times the K steps and prints the line (metric, value, ms_per_step, the kernel table and the
+rooflines of the timed steps).  --dump-outputs DIR writes what the last timed step returned (a seeded sample of its queries, .npy files).
+Everything else -- the blocking and prefilter-alone steps, the CPU baseline and the result digests against the reference, the config-4,
+end-to-end and config-5 legs described below -- runs only with --full.
 
 A step = one full pass of the hot path (query-side derivation, k-mer prefilter, ungapped diagonal
 scoring, hit selection, gapped SW forward/reverse, e-values) over one batch of synthetic ORF
@@ -14,8 +19,8 @@ Multi-GPU = query sharding, no collective on the data path (only the timing barr
   --scaling weak   every rank searches its own 10k contigs.
 Every rank holds a full replica of the target index.
 
-The JSON line carries `result_digest`: SHA-256 digests over the formatted prefilter hits and alignments of the last
-timed step -- ALL of its queries by default, in pieces of --cpu-sample queries -- next to the same digests of what the
+With --full the JSON line carries `result_digest`: SHA-256 digests over the formatted prefilter hits and alignments of the last
+timed step -- ALL of its queries by default, in pieces of --cpu-sample queries, as far as --digest-budget seconds reach -- next to the same digests of what the
 reference's own code (oracle/_ref/ref_harness) wrote for the same queries on this box's host cores, outside the timed
 region.  The CPU baseline is TIMED on the first piece only (a bounded sample).  "bit-exact" is checked, not asserted: the
 metric string says "(bit-exact hits)" only when that comparison ran and matched, "(hits UNVERIFIED ...)" when it did not run.
@@ -101,6 +106,41 @@ def gpu_digest(api, hits, hoff, alns, aoff, n, first=0):
     hb = api.format_hits_bulk(hits, int(hoff[first]), int(hoff[first + n]))
     ab = api.format_alignments_bulk(alns, int(aoff[first]), int(aoff[first + n]))
     return {"prefilter": oracle.digest_arrays(hoff[first:first + n + 1], hb, n), "alignments": oracle.digest_arrays(aoff[first:first + n + 1], ab, n)}
+
+
+DUMP_QUERIES = 32768              # queries of a --dump-outputs sample
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # what the sample's records may take as float64 (the dump stays under 64 MB with the files' headers)
+
+
+def dump_outputs(api, outdir, hits, hoff, alns, aoff, seed):
+    """--dump-outputs: what the timed path returned to its caller in the last timed step -- the prefilter hits and the alignments per query -- as
+    float64 .npy files (every field is a 16/32-bit integer, a float or a double: exact in float64).  The step returns 70 M hits and 6 M alignments
+    on the headline workload, so the records of a SAMPLE of the queries are written: the first DUMP_QUERIES of a permutation of the queries drawn
+    from `seed` alone (halved until their records fit the budget), in query order.  totals.npy carries the counts over ALL queries."""
+    os.makedirs(outdir, exist_ok=True)
+    hoff, aoff = np.asarray(hoff).astype(np.int64), np.asarray(aoff).astype(np.int64)
+    n = len(hoff) - 1
+    hcnt, acnt = np.diff(hoff), np.diff(aoff)
+    adt = np.dtype(api.Alignment)
+    alns = np.frombuffer(alns, dtype=adt) if len(alns) else np.zeros(0, dtype=adt)
+    hit_fields, aln_fields = ("seq_id", "pref_score", "diagonal"), adt.names
+    order = np.random.default_rng(seed).permutation(n)
+    cost = 8 * (3 + len(hit_fields) * hcnt + len(aln_fields) * acnt)
+    k = min(n, DUMP_QUERIES)
+    while k > 1 and int(cost[order[:k]].sum()) > DUMP_BUDGET_BYTES:
+        k //= 2
+    take = np.sort(order[:k])
+
+    def rows(off, cnt):                            # the record numbers of the sampled queries, query by query
+        c = cnt[take]
+        return np.repeat(off[:-1][take] - (np.cumsum(c) - c), c) + np.arange(int(c.sum()), dtype=np.int64)
+    hr, ar = rows(hoff, hcnt), rows(aoff, acnt)
+    out = {"totals": np.array([n, hoff[-1], aoff[-1]]),                     # queries, prefilter hits, alignments of the whole step
+           "sample_queries": take, "hit_counts": hcnt[take], "alignment_counts": acnt[take],
+           "hits": np.stack([hits[f][hr] for f in hit_fields], axis=1),       # columns: seq_id, pref_score, diagonal
+           "alignments": np.stack([alns[f][ar] for f in aln_fields], axis=1)}  # columns: the fields of mk_alignment in their order
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(targets, queries, budget_queries, threads, first=0):
@@ -477,6 +517,9 @@ def main():
                     "from that one file (mk_targetdb_open_index) instead of masking and indexing its own replica")
     ap.add_argument("--digest-queries", type=int, default=-1, help="queries of the last timed step whose hits and alignments are compared with the reference's own "
                     "run (-1 = all of them, in pieces of --cpu-sample queries outside the timed region; 0 = only the CPU-baseline sample)")
+    ap.add_argument("--digest-budget", type=float, default=180.0, help="seconds of CPU-baseline and digest runs after which no further piece of --digest-queries is "
+                    "begun: the reference harness covers all queries of the headline workload in 120 s on 16 cores; the C oracle port, which stands in where the "
+                    "harness is not built, is five times slower and covers what it can")
     ap.add_argument("--e2e-sample", type=int, default=500, help="contigs of the end-to-end leg (`metaeuk-amd predictexons` over DBs on disk, N = 1 only) whose exon sets are "
                     "compared with the reference's chain; -1 = skip the leg")
     ap.add_argument("--config5-targets", type=int, default=60000000, help="BASELINE config 5's target side beside the headline number (N = 1 only, a process of its own): "
@@ -487,11 +530,19 @@ def main():
     ap.add_argument("--config5-timeout", type=int, default=900)
     ap.add_argument("--config5-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--config4-sample", type=int, default=2048, help="profiles of the config-4 leg whose hits and alignments are compared with the reference")
+    ap.add_argument("--full", action="store_true", help="beside the headline figure: the blocking and prefilter-alone steps, the CPU baseline and the result digest "
+                    "against the reference, the config-4, end-to-end and config-5 legs (each as its own option sizes it).  Without it a run sets up, warms "
+                    "up, times the steps and prints the line; the options of those legs have no effect")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps: write the hits and alignments of a seeded sample of the last "
+                    "timed step's queries as DIR/<name>.npy (float64; dump_outputs)")
     args = ap.parse_args()
 
     if args.config5_only:
         print(json.dumps(config5_leg_child(args)))
         return
+    if not args.full:
+        args.blocking_steps = args.alone_steps = args.cpu_sample = args.config4_profiles = args.config5_targets = 0
+        args.e2e_sample = -1
     # the one JSON line goes to the real stdout; whatever libraries print there (RCCL's version banner at communicator creation) is
     # sent to stderr instead
     real_stdout = os.fdopen(os.dup(1), "w")
@@ -614,6 +665,11 @@ def main():
     barrier()
     elapsed = time.time() - t0
     stats = api.kernel_stats()
+    if args.dump_outputs:
+        if not last:
+            raise SystemExit("--dump-outputs needs a timed step (--steps >= 1)")
+        dump_outputs(api, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     last["hits"], last["hoff"], last["alns"], last["aoff"], args.seed)
     blocking = None
     if not (args.two_calls or args.blocking) and args.blocking_steps > 0:
         # the same step with the blocking call, one batch at a time (round 4's figure), outside the headline region
@@ -743,6 +799,7 @@ def main():
     if rank == 0:
         if world == 1 and args.cpu_sample > 0:
             n_s = min(args.cpu_sample, nq)
+            t_cpu = time.time()
             try:
                 line["cpu_baseline"] = cpu_baseline(targets, queries, n_s, int(api.lib().mk_host_threads()))
             except Exception as e:  # the baseline is reported, never required
@@ -761,7 +818,7 @@ def main():
                 want = nq if args.digest_queries < 0 else min(nq, max(n_s, args.digest_queries))
                 t_more = time.time()
                 at = n_s
-                while c and at < want:
+                while c and at < want and time.time() - t_cpu < args.digest_budget:      # (`covered` says how far it came)
                     m = min(n_s, want - at)
                     cb = cpu_baseline(targets, queries, m, int(api.lib().mk_host_threads()), first=at)
                     gp = gpu_digest(api, last["hits"], last["hoff"], last["alns"], last["aoff"], m, first=at)

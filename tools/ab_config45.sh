@@ -3,7 +3,7 @@
 O=gpurun_out/$1; shift; mkdir -p $O
 for v in "$@"; do
   if [ $v = product ]; then unset METAEUK_AMD_LIB; else export METAEUK_AMD_LIB=$PWD/tools/_variants/libmetaeuk_amd_$v.so; fi
-  python bench.py --steps 1 --warmup 0 --cpu-sample 0 --config4-profiles 50000 --config4-sample 0 --e2e-sample -1 --blocking-steps 0 --alone-steps 0 --config5-digest 0 > $O/b_$v.json 2> $O/b_$v.err
+  python bench.py --full --steps 1 --warmup 0 --cpu-sample 0 --config4-profiles 50000 --config4-sample 0 --e2e-sample -1 --blocking-steps 0 --alone-steps 0 --config5-digest 0 > $O/b_$v.json 2> $O/b_$v.err
   python - $O/b_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

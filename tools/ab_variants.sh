@@ -2,7 +2,7 @@
 # A/B of library variants on ONE box: tools/ab_variants.sh <out dir under gpurun_out> <variant names ...>   ("product" = the in-tree library)
 O=gpurun_out/$1; shift
 mkdir -p $O
-ARGS=${AB_ARGS:---steps 8 --warmup 3 --cpu-sample 0 --config4-profiles 0 --e2e-sample -1 --config5-targets 0 --blocking-steps 0}
+ARGS=${AB_ARGS:---full --steps 8 --warmup 3 --cpu-sample 0 --config4-profiles 0 --e2e-sample -1 --config5-targets 0 --blocking-steps 0}
 for v in "$@"; do
   # name[.tag][@VAR=value[,VAR=value]]: environment of the run after the @ (separate with + instead when a value holds commas)
   envs=""; case $v in *@*) envs=${v#*@}; v=${v%%@*};; esac
