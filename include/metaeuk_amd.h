@@ -87,6 +87,18 @@ typedef struct {
                                  6 or 7 force it.  k = 7: spaced seed 11010110011 (Sequence.h:25), threshold 186.15 - 11.22 s
                                  (Prefiltering.cpp:1057-1059), 2-mer x 2-mer x 3-mer k-mer lists (KmerGenerator.cpp:41-86), a 20^7-cell
                                  table (10 GB of HBM).  The target side decides; a query batch follows the database it is searched against */
+    /* the result filters of the searchworkflow flag list (Parameters.cpp:74-75,81; Util::canBeCovered / Util::hasCoverage, Util.cpp:477-511;
+     * Alignment::checkCriteria, Alignment.cpp:548-567).  All 0 = no filter.  The prefilter drops the hits whose two LENGTHS cannot reach cov_thr
+     * (cov modes 0, 2 and 5 only, Prefiltering.cpp:856-863); the alignment stage never scores such a pair (any mode, Alignment.cpp:370), skips the
+     * start-position pass of a pair whose coverage over (0, end cell) misses the threshold (StripedSmithWaterman.cpp:389-398) and keeps an
+     * alignment only if its final coverage and its sequence identity (the score-per-column estimate of --alignment-mode 2) pass.  The kept
+     * records and their order are those of the unfiltered run.  Outside [0, 1] / 0..5: MK_ERR_ARG.  Not with profile queries
+     * (profile_search = 1: the reference swaps the coverage mode for the inverted search, Search.cpp:370-396): MK_ERR_UNSUPPORTED. */
+    float cov_thr;            /* -c            0 .. 1 */
+    int cov_mode;             /* --cov-mode    0: query and target, 1: target, 2: query, 3: target length >= x query length (and <= it),
+                                 4: query length >= x target length (and <= it), 5: shorter length >= x longer length (Parameters.h:277-282) */
+    float seq_id_thr;         /* --min-seq-id  0 .. 1 */
+    int pad_;
 } mk_params;
 
 /* ---- process-wide ---- */
@@ -96,6 +108,10 @@ void mk_default_params(mk_params *p);       /* defaults of `metaeuk predictexons
 int mk_device_name(char *buf, size_t cap);
 int mk_device_memory(uint64_t *free_bytes, uint64_t *total_bytes);   /* HBM of the bound GPU (the split planner of the commands sizes the target side with it) */
 int mk_host_threads(void);                  /* CPUs usable by this process (affinity and cgroup quota) */
+/* the result filters of `p` on one pair, host code without a GPU: 1 = keep, 0 = drop, MK_ERR_ARG for values outside their range.
+ * a == NULL: the test on the two lengths alone (Util::canBeCovered); else also Util::hasCoverage on a->qcov / a->dbcov and
+ * (double) a->seq_id >= (double) p->seq_id_thr.  The host paths of the library decide with it. */
+int mk_result_filter(const mk_params *p, int q_len, int t_len, const mk_alignment *a /* NULL: length test only */);
 
 /* ---- encoding: Sequence::mapSequence + SubstitutionMatrix::aa2num (Sequence.cpp:307-324) ---- */
 void mk_encode(const char *ascii, size_t len, uint8_t *codes);

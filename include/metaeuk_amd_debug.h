@@ -28,6 +28,9 @@ int mk_synth_seqdb(const uint8_t *residues, const uint64_t *offsets, uint64_t n,
  * data and 6e7 index rows.  with_lines != 0: <base>.txt too, one sequence per line (what oracle/ref_harness reads). */
 int mk_synth_write_seqdb(const char *base, const uint8_t *residues, const uint64_t *offsets, uint64_t n, int with_lines);
 
+/* sizeof(mk_params) of this build: a binding that mirrors the struct (metaeuk_amd/api.py) checks its own layout against it */
+size_t mk_debug_params_size(void);
+
 /* ---- experiment hook (tools/micro/mk_experiments.hip is its only user): the device view of a (database, batch) pair -- a
  * mk::PrefilterDeviceView (metaeuk_amd/csrc/mk_prefilter.hpp: pointers into HBM, valid while both handles live) copied into view_out, whose
  * size must be given as view_bytes -- and the batch's host offsets.  The layout of that struct is NOT stable across builds. */

@@ -19,7 +19,8 @@ class Params(C.Structure):
                 ("mask", C.c_int), ("mask_prob", C.c_float), ("gap_open", C.c_int), ("gap_extend", C.c_int),
                 ("evalue_thr", C.c_double), ("min_aln_len", C.c_int), ("simd_lanes_byte", C.c_int),
                 ("simd_lanes_word", C.c_int), ("simd_lanes_double", C.c_int), ("host_l2_bytes", C.c_uint64),
-                ("profile_search", C.c_int), ("kmer_size", C.c_int)]
+                ("profile_search", C.c_int), ("kmer_size", C.c_int),
+                ("cov_thr", C.c_float), ("cov_mode", C.c_int), ("seq_id_thr", C.c_float), ("pad_", C.c_int)]   # -c, --cov-mode, --min-seq-id
 
 
 class Hit(C.Structure):
@@ -49,7 +50,7 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_profiles_create", "mk_profiles_derived", "mk_swap_alignments", "mk_swapped_result", "mk_swapped_destroy",
            "mk_targetdb_masked_residues", "mk_targetdb_kmer_size", "mk_targetdb_longest_list", "mk_targetdb_index_compare",
            "mk_synth_targets", "mk_synth_fragments", "mk_synth_seqdb", "mk_synth_write_seqdb", "mk_targetdb_create_sequences", "mk_prefilter_statistics",
-           "mk_format_prefilter_statistics", "mk_device_memory"]
+           "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size"]
 
 
 def lib():
@@ -70,6 +71,7 @@ def lib():
         L.mk_format_alignments.restype = C.c_size_t
         L.mk_format_orf_header.restype = C.c_size_t
         L.mk_format_prediction_exon.restype = C.c_size_t
+        L.mk_debug_params_size.restype = C.c_size_t
         _LIB = L
     return _LIB
 
@@ -91,6 +93,14 @@ def default_params():
     p = Params()
     lib().mk_default_params(C.byref(p))
     return p
+
+
+def result_filter(params, q_len, t_len, aln=None):
+    """-c / --cov-mode / --min-seq-id of `params` on one pair (host code, no GPU): True = keep.  aln = None: the test on the lengths only"""
+    rc = lib().mk_result_filter(C.byref(params), C.c_int(int(q_len)), C.c_int(int(t_len)), None if aln is None else C.byref(aln))
+    if rc < 0:
+        _chk(rc)
+    return rc == 1
 
 
 def device_name():

@@ -4,6 +4,7 @@
 // entry point fails with MK_ERR_DEVICE.
 #include "../../include/metaeuk_amd_debug.h"
 #include "mk_align.hpp"
+#include "mk_filters.hpp"
 #include "mk_host.hpp"
 #include "mk_kernels.hpp"
 #include "mk_orf.hpp"
@@ -510,6 +511,29 @@ void mk_default_params(mk_params *p) {
     p->host_l2_bytes = 1048576;
     p->profile_search = 0;
     p->kmer_size = 0;
+    p->cov_thr = 0.0f; p->cov_mode = 0; p->seq_id_thr = 0.0f; p->pad_ = 0;
+}
+
+size_t mk_debug_params_size(void) { return sizeof(mk_params); }
+
+// -c / --cov-mode / --min-seq-id of a call: values in range; not for profile queries (the reference swaps the coverage mode for the inverted
+// search, Search.cpp:370-396, which is not restated)
+static int check_filters(const mk_params *P, bool profiles) {
+    const mk::ResultFilter F = mk::result_filter_of(*P);
+    if (!mk::filter_in_range(F))
+        return fail(MK_ERR_ARG, "result filters out of range: -c %g --cov-mode %d --min-seq-id %g (thresholds in [0, 1], coverage modes 0 to 5)", (double) P->cov_thr, P->cov_mode, (double) P->seq_id_thr);
+    if (profiles && (P->cov_thr > 0.0f || P->seq_id_thr > 0.0f || P->cov_mode != 0))
+        return fail(MK_ERR_UNSUPPORTED, "-c / --cov-mode / --min-seq-id with profile queries (the inverted search of a profile target database) are not implemented");
+    return MK_OK;
+}
+
+int mk_result_filter(const mk_params *p, int q_len, int t_len, const mk_alignment *a) {
+    if (!p) return fail(MK_ERR_ARG, "null argument");
+    const int rc = check_filters(p, false);
+    if (rc != MK_OK) return rc;
+    if (!mk::can_be_covered(p->cov_thr, p->cov_mode, static_cast<float>(q_len), static_cast<float>(t_len))) return 0;
+    if (a && !(mk::has_coverage(p->cov_thr, p->cov_mode, a->qcov, a->dbcov) && mk::seq_id_ok(a->seq_id, p->seq_id_thr))) return 0;
+    return 1;
 }
 
 void mk_encode(const char *ascii, size_t len, uint8_t *codes) { mk::encode(ascii, len, codes); }
@@ -551,6 +575,7 @@ static int targetdb_create(const uint8_t *residues, const uint64_t *offsets, uin
     if (!residues || !offsets || !P || !out) return fail(MK_ERR_ARG, "null argument");
     // IndexTable::computeKmerSize (IndexTable.h:439-449): from 3.35e9 target residues on the reference searches with k = 7
     if (P->kmer_size != 0 && P->kmer_size != 6 && P->kmer_size != 7) return fail(MK_ERR_UNSUPPORTED, "-k %d: k-mer sizes 6 and 7 are implemented", P->kmer_size);
+    if ((rc = check_filters(P, P->profile_search != 0)) != MK_OK) return rc;
     const int kmerSize = prebuilt ? prebuilt->kmerSize : (P->kmer_size ? P->kmer_size : (offsets[n] < 3350000000ull ? 6 : 7));
     if (prebuilt && P->kmer_size && P->kmer_size != kmerSize) return fail(MK_ERR_ARG, "-k %d, but the index DB was built with k = %d", P->kmer_size, kmerSize);
     mk_targetdb *db = new mk_targetdb();
@@ -1367,6 +1392,7 @@ int mk_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
     if ((rc = check_indexed(db, "mk_prefilter")) != MK_OK) return rc;
     if ((rc = check_roles(db, q)) != MK_OK) return rc;
+    if ((rc = check_filters(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
     if ((rc = match_kmer_size(db, q)) != MK_OK) return rc;
     std::string err;
     const int binCount = mk::bin_count_for(db->n, P->host_l2_bytes);
@@ -1458,7 +1484,7 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
                        const mk::AssembleTables *tables, hipStream_t stream, size_t &nAlnOut, const std::function<void()> &wait_turn = nullptr) {
     const uint32_t nqc = q1 - q0;
     const uint64_t h0 = q->hitOff[q0];
-    const size_t n = (size_t) (q->hitOff[q1] - h0);
+    size_t n = (size_t) (q->hitOff[q1] - h0);
     const mk_hit *hits = (const mk_hit *) q->hits.p + h0;
     std::vector<uint64_t> hitOff((size_t) nqc + 1);            // pair offsets of the range
     for (uint32_t i = 0; i <= nqc; i++) hitOff[i] = q->hitOff[(size_t) q0 + i] - h0;
@@ -1494,6 +1520,8 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
         return MK_OK;
     }
     HostTimer ht("host_align_assemble");
+    // (a result filter: the records name pairs of the stage's own list, without the pairs the length test removed)
+    if (asmArgs.hitsCut) { hits = asmArgs.hitsCut; std::copy(asmArgs.hitOffCut, asmArgs.hitOffCut + nqc + 1, hitOff.begin()); n = (size_t) asmArgs.cutPairs; }
     // raw is ordered by pair index == by query: query i owns raw[first[i] .. first[i+1])
     std::vector<uint64_t> first((size_t) nqc + 1);
 #pragma omp parallel for schedule(static)
@@ -1516,6 +1544,7 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
         uint64_t w = begin;
         for (uint64_t k = first[i]; k < first[i + 1]; k++) {
             const mk::AlnRaw &r = raw[k];
+            if (r.q_start == mk::ALN_SKIPPED) continue;       // the coverage gate of a result filter dropped the pair before the reverse pass
             if (r.q_start == -2) { mismatch++; continue; }
             const uint32_t t = hits[r.pair].seq_id;
             const int tLen = (int) (db->off[t + 1] - db->off[t]);
@@ -1533,7 +1562,7 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
             sid = std::min(sid, 1.0f);
             a.seq_id = std::max(0.0f, sid);
             a.bit_score = static_cast<int>(db->evaluer.bitScore((double) r.score) + 0.5);
-            if (a.evalue <= P->evalue_thr && a.aln_len >= P->min_aln_len) alns[w++] = a;
+            if (a.evalue <= P->evalue_thr && a.aln_len >= P->min_aln_len && mk_result_filter(P, qLen, tLen, &a) == 1) alns[w++] = a;
         }
         if (w - begin > 1) {
             if (db->keys.empty()) std::sort(alns + begin, alns + w, mk::alignment_less);
@@ -1562,6 +1591,7 @@ int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
     if (!q->havePref) return fail(MK_ERR_ARG, "mk_align: the batch has no prefilter result");
     if ((rc = check_roles(db, q)) != MK_OK) return rc;
+    if ((rc = check_filters(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
     HostTimer htAll("host_align_total");
     std::shared_ptr<const ScoreTabs> tabs;
     {
@@ -1817,6 +1847,7 @@ int mk_search_begin(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if (q->job) return fail(MK_ERR_ARG, "mk_search_begin: a search of this batch is in flight (mk_search_wait collects it)");
     if ((rc = check_indexed(db, "mk_search")) != MK_OK) return rc;
     if ((rc = check_roles(db, q)) != MK_OK) return rc;
+    if ((rc = check_filters(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
     SearchJob *job = new SearchJob();
     job->db = db; job->q = q; job->P = *P;
     job->hostThreads = omp_get_max_threads();

@@ -16,7 +16,14 @@
 //   sw_kernel                position pass (end cell of the maximum), then rev_jobs_kernel + reverse pass on the reversed
 //                            prefixes (start cell)
 //   collect_kernel           AlnRaw records in pair order
+// With a result filter set (-c / --cov-mode / --min-seq-id, mk_filters.hpp) three cuts are added, none of them inside a DP:
+//   cut_count / cut_emit     the pairs whose two lengths cannot reach the coverage threshold leave the stage's copy of the hit list before
+//                            anything is planned (Alignment.cpp:370)
+//   rev_jobs_kernel<true>    a survivor whose coverage over (0, end cell) misses the threshold gets no reverse job
+//                            (StripedSmithWaterman.cpp:389-398); collect_kernel marks it (q_start == ALN_SKIPPED)
+//   assemble_kernel          the final coverage and the sequence identity join the criteria (Alignment.cpp:548-567)
 #include "mk_align.hpp"
+#include "mk_filters.hpp"
 #include "mk_kernels.hpp"
 #include "mk_segsort.hpp"
 #include <algorithm>
@@ -44,6 +51,48 @@ __device__ __forceinline__ uint32_t sort_key(uint32_t qLen, uint32_t tLen) { ret
 
 // short launches of this stage run beside the persistent workgroups of the prefilter (mk_search): they ask for issue priority
 __device__ __forceinline__ void helper_prio() { __builtin_amdgcn_s_setprio(3); }
+
+// ---- length cut (result filters): the hits of a query whose lengths can reach the coverage threshold, in their order.  One wave per query.
+__global__ __launch_bounds__(256) void cut_count_kernel(AlignView V, const uint64_t *hitOff, const mk_hit *hits, ResultFilter F, uint32_t *cnt) {
+    helper_prio();
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (q >= V.n_queries) return;
+    const float qLen = (float) (uint32_t) (V.q_off[q + 1] - V.q_off[q]);
+    const uint64_t p0 = hitOff[q], p1 = hitOff[q + 1];
+    uint32_t c = 0;
+    for (uint64_t b = p0; b < p1; b += 64) {
+        const uint64_t p = b + lane;
+        bool keep = false;
+        if (p < p1) {
+            const uint32_t t = hits[p].seq_id;
+            keep = t >= V.n_targets || can_be_covered(F.cov_thr, F.cov_mode, qLen, (float) (uint32_t) (V.t_off[t + 1] - V.t_off[t]));   // (a target outside the DB is reported by expand_pairs)
+        }
+        c += (uint32_t) __popcll(__ballot(keep));
+    }
+    if (lane == 0) cnt[q] = c;
+}
+__global__ __launch_bounds__(256) void cut_emit_kernel(AlignView V, const uint64_t *hitOff, const mk_hit *hits, ResultFilter F, const uint32_t *newOff /* [nq + 1] */,
+                                                       uint64_t *hitOffOut, mk_hit *hitsOut) {
+    helper_prio();
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (q >= V.n_queries) return;
+    const float qLen = (float) (uint32_t) (V.q_off[q + 1] - V.q_off[q]);
+    const uint64_t p0 = hitOff[q], p1 = hitOff[q + 1];
+    uint32_t w = newOff[q];
+    if (lane == 0) { hitOffOut[q] = w; if (q + 1 == V.n_queries) hitOffOut[q + 1] = newOff[q + 1]; }
+    for (uint64_t b = p0; b < p1; b += 64) {
+        const uint64_t p = b + lane;
+        bool keep = false;
+        mk_hit h;
+        if (p < p1) {
+            h = hits[p];
+            keep = h.seq_id >= V.n_targets || can_be_covered(F.cov_thr, F.cov_mode, qLen, (float) (uint32_t) (V.t_off[h.seq_id + 1] - V.t_off[h.seq_id]));
+        }
+        const unsigned long long m = __ballot(keep);
+        if (keep) hitsOut[w + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = h;
+        w += (uint32_t) __popcll(m);
+    }
+}
 
 // pair -> forward job (the query of pair p is the one whose hit range holds p)
 __global__ __launch_bounds__(256) void expand_pairs_kernel(AlignView V, const uint64_t *hitOff, const mk_hit *hits, uint64_t n,
@@ -284,22 +333,35 @@ __global__ __launch_bounds__(256) void gate_emit_kernel(const SwJob *fwdJobs, co
 
 // reverse jobs (reversed prefixes ending at the forward end cell) of the survivors; the position pass must reproduce the
 // score the gate saw
+// COVGATE (a result filter is set): the reference's early exit -- a survivor whose coverage over (0, end cell) misses the threshold gets no
+// reverse job; its reverse result carries ALN_SKIPPED instead of a score.  The jobs that remain are numbered by a counter (their order does not
+// matter: they are binned by length next, and every job writes to the slot of its survivor).
+template <bool COVGATE>
 __global__ __launch_bounds__(256) void rev_jobs_kernel(const SwJob *posJobs, const SwOut *posOut, const uint32_t *posPair, const SwOut *fwdOut, uint32_t n,
-                                                       SwJob *revJobs, uint32_t *revKeys, uint32_t *hist, uint32_t *mismatch) {
+                                                       SwJob *revJobs, uint32_t *revKeys, uint32_t *hist, uint32_t *mismatch,
+                                                       const SwJob *fwdJobs, ResultFilter F, SwOut *revOut, uint32_t *nRevJobs) {
     helper_prio();
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const SwOut o = posOut[r];
     const SwJob f = posJobs[r];
     if (o.score != fwdOut[posPair[r]].score || o.end_row < 0 || o.end_col < 0) atomicAdd(mismatch, 1u);
+    uint32_t at = r;
+    if constexpr (COVGATE) {
+        const uint32_t qLen = f.q_len, tLen = fwdJobs[posPair[r]].t_len;        // (the position job's columns may end at the score pass's bound)
+        const float qCov = (float) (min(qLen, (uint32_t) max(o.end_row, 0)) + 1u) / (float) qLen;      // computeCov(0, end, len)
+        const float tCov = (float) (min(tLen, (uint32_t) max(o.end_col, 0)) + 1u) / (float) tLen;
+        if (!has_coverage(F.cov_thr, F.cov_mode, qCov, tCov)) { revOut[r].score = ALN_SKIPPED; return; }
+        at = atomicAdd(nRevJobs, 1u);
+    }
     SwJob j;
     j.q_len = (uint32_t) max(o.end_row, 0) + 1; j.t_len = (uint32_t) max(o.end_col, 0) + 1;
     j.q_start = f.q_start + (uint32_t) max(o.end_row, 0); j.q_step = -1;
     j.t_start = f.t_start + (uint64_t) max(o.end_col, 0); j.t_step = -1;
     j.slot = r;
-    revJobs[r] = j;
+    revJobs[at] = j;
     const uint32_t key = sort_key(j.q_len, j.t_len);
-    revKeys[r] = key;
+    revKeys[at] = key;
     atomicAdd(&hist[key], 1u);
 }
 
@@ -348,7 +410,8 @@ __global__ __launch_bounds__(256) void collect_kernel(const uint32_t *posPair, u
     AlnRaw a;
     a.pair = posPair[i]; a.score = f.score; a.q_end = f.end_row; a.t_end = f.end_col;
     // reverse score kept in q_start when it disagrees (the reference EXITs on that, :466-473)
-    if (b.score != f.score) { a.q_start = -2; a.t_start = b.score; }
+    if (b.score == ALN_SKIPPED) { a.q_start = ALN_SKIPPED; a.t_start = 0; }          // no reverse pass: the coverage gate dropped the pair
+    else if (b.score != f.score) { a.q_start = -2; a.t_start = b.score; }
     else { a.q_start = f.end_row - b.end_row; a.t_start = f.end_col - b.end_col; }
     out[i] = a;
 }
@@ -359,7 +422,7 @@ struct AssembleView {
     const uint64_t *hitOff; const mk_hit *hits; uint32_t nq;
     const uint64_t *q_off; const uint64_t *t_off;
     const double *evalTab; const int32_t *lenIdx; uint32_t maxLen, smax; const int32_t *bitScore; const uint32_t *sortKey;
-    double evalThr; int minAlnLen;
+    double evalThr; int minAlnLen; ResultFilter filter;
     mk_alignment *tmp; uint8_t *pass; uint32_t *flags /* [0] score beyond the table [1] forward/backward mismatch */;
     unsigned long long *revWork;     // [2 * cfg]: bytes, [2 * cfg + 1]: cells of the reverse pass (statistics)
 };
@@ -370,7 +433,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleView A) {
     for (int k = threadIdx.x; k < 2 * SW_NCFG; k += blockDim.x) sWork[k] = 0;
     __syncthreads();
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < A.n) {
+    if (i < A.n && A.raw[i].q_start != ALN_SKIPPED) {
         const uint32_t ql = (uint32_t) A.raw[i].q_end + 1u, tl = (uint32_t) A.raw[i].t_end + 1u;
         const int c = sw_cfg_of(ql);
         atomicAdd(&sWork[2 * c], (unsigned long long) (tl + 2u * ql + (uint32_t) (sizeof(SwJob) + sizeof(SwOut))));
@@ -381,6 +444,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleView A) {
     if (i >= A.n) return;
     const AlnRaw r = A.raw[i];
     A.pass[i] = 0;
+    if (r.q_start == ALN_SKIPPED) return;
     if (r.q_start == -2) { atomicAdd(&A.flags[1], 1u); return; }
     uint32_t lo = 0, hi = A.nq;                       // largest q with hitOff[q] <= pair
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (A.hitOff[mid] <= (uint64_t) r.pair) lo = mid; else hi = mid; }
@@ -403,7 +467,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleView A) {
     a.seq_id = fmaxf(0.0f, sid);
     a.bit_score = A.bitScore[r.score];
     A.tmp[i] = a;
-    A.pass[i] = (a.evalue <= A.evalThr && a.aln_len >= A.minAlnLen) ? 1 : 0;
+    A.pass[i] = (a.evalue <= A.evalThr && a.aln_len >= A.minAlnLen && has_coverage(A.filter.cov_thr, A.filter.cov_mode, a.qcov, a.dbcov) &&
+                 seq_id_ok(a.seq_id, A.filter.seq_id_thr)) ? 1 : 0;
 }
 
 
@@ -804,8 +869,10 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
     if (assemble) { assemble->done = assemble->tables != nullptr; assemble->nOut = 0; if (assemble->counts) std::fill(assemble->counts, assemble->counts + V.n_queries, 0u); }
     if (nPairs == 0) return MK_OK;
     if (nPairs >= 0x7FFFFFFFull) { err = "more than 2^31 pairs in one batch: split the batch"; return MK_ERR_UNSUPPORTED; }
-    const uint32_t n = (uint32_t) nPairs;
-    const uint32_t nGateBlocks = (n + 255u) / 256u;
+    if (assemble) { assemble->cutPairs = nPairs; assemble->hitOffCut = nullptr; assemble->hitsCut = nullptr; }
+    else if (filters_active(result_filter_of(P))) { err = "internal: a result filter needs the caller's assembly arguments"; return MK_ERR_ARG; }
+    uint32_t n = (uint32_t) nPairs;
+    uint32_t nGateBlocks = (n + 255u) / 256u;
     uint64_t *dHitOff = (uint64_t *) dev_scratch("align_hitoff", ((size_t) V.n_queries + 1) * sizeof(uint64_t));
     mk_hit *dHits = (mk_hit *) dev_scratch("align_hits", (size_t) n * sizeof(mk_hit));
     SwJob *dJobs = (SwJob *) dev_scratch("align_jobs", (size_t) n * sizeof(SwJob));
@@ -825,7 +892,39 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
     unsigned long long *hFwdWork = (unsigned long long *) pinned_scratch("align_fwdwork_h", 2 * SW_NCFG * 8);
     ANULL(dFwdWork); ANULL(hFwdWork);
     ACHK(hipMemsetAsync(dFwdWork, 0, 2 * SW_NCFG * 8, stream));
-    int th = tb("align_expand", 44.0 * n, 0);
+    const ResultFilter F = result_filter_of(P);
+    const bool filtered = filters_active(F);
+    uint32_t *hCount = (uint32_t *) pinned_scratch("align_count_h", 16);
+    ANULL(hCount);
+    int th;
+    if (filtered) {
+        // length cut: the stage goes on with a compacted copy of the hit list (the planner, the job order and the assembly all read the same one);
+        // the caller's list is left alone
+        const uint32_t nq = V.n_queries;
+        uint32_t *dCutCnt = (uint32_t *) dev_scratch("align_cutcnt", ((size_t) nq + 1) * 4);
+        uint64_t *dHitOffCut = (uint64_t *) dev_scratch("align_hitoff_cut", ((size_t) nq + 1) * sizeof(uint64_t));
+        mk_hit *dHitsCut = (mk_hit *) dev_scratch("align_hits_cut", (size_t) n * sizeof(mk_hit));
+        ANULL(dCutCnt); ANULL(dHitOffCut); ANULL(dHitsCut);
+        th = tb("align_cut", 2.0 * (double) n * sizeof(mk_hit), 0);
+        hipLaunchKernelGGL(cut_count_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, V, (const uint64_t *) dHitOff, (const mk_hit *) dHits, F, dCutCnt);
+        ACHK(hipGetLastError());
+        int rcs = device_scan(dCutCnt, nq, dCutCnt, dCutCnt + nq, stream, err);
+        if (rcs != MK_OK) return rcs;
+        hipLaunchKernelGGL(cut_emit_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, V, (const uint64_t *) dHitOff, (const mk_hit *) dHits, F, (const uint32_t *) dCutCnt,
+                           dHitOffCut, dHitsCut);
+        te(th);
+        ACHK(hipGetLastError());
+        ACHK(hipMemcpyAsync(hCount, dCutCnt + nq, 4, hipMemcpyDeviceToHost, stream));
+        ACHK(sync_wait(stream, "wait_align"));
+        const uint32_t nKept = hCount[0];
+        if (nKept > n) { err = "internal: the length cut kept more pairs than it was given"; return MK_ERR_DEVICE; }
+        dHitOff = dHitOffCut; dHits = dHitsCut;
+        assemble->cutPairs = nKept;
+        if (nKept == 0) return MK_OK;
+        n = nKept;
+        nGateBlocks = (n + 255u) / 256u;
+    }
+    th = tb("align_expand", 44.0 * n, 0);
     hipLaunchKernelGGL(expand_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, V, dHitOff, dHits, (uint64_t) n, dJobs, dCount + 1, dFwdWork);
     te(th);
     ACHK(hipGetLastError());
@@ -844,8 +943,6 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
     hipLaunchKernelGGL(gate_count_kernel, dim3(nGateBlocks), dim3(256), 0, stream, dJobs, dOut, (uint64_t) n, dGate, dGateBlk);
     ACHK(hipGetLastError());
     if ((rc = device_scan(dGateBlk, nGateBlocks, dGateBlk, dCount, stream, err)) != MK_OK) return rc;
-    uint32_t *hCount = (uint32_t *) pinned_scratch("align_count_h", 16);
-    ANULL(hCount);
     ACHK(hipMemcpyAsync(hCount, dCount, 8, hipMemcpyDeviceToHost, stream));
     ACHK(sync_wait(stream, "wait_align"));
     if (hCount[1] != 0) { err = "prefilter hit " + std::to_string(hCount[1] - 1) + " names a target outside the DB"; return MK_ERR_ARG; }
@@ -870,9 +967,22 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
     rc = run_sorted_sw(V, P, dPosJobs, dPosOut, dKeys, dHist, dOrder, nRev, "sw_pos", stream, err, tb, te, hPos, dPosScore);
     if (rc != MK_OK) return rc;
     set_range_work(hPos, hPosWork, ts);
-    hipLaunchKernelGGL(rev_jobs_kernel, dim3((nRev + 255) / 256), dim3(256), 0, stream, dPosJobs, dPosOut, dRevPair, dOut, nRev, dRevJobs, dKeys, dHist, dCount + 2);   // (bin_scan cleared the histogram)
-    ACHK(hipGetLastError());
-    rc = run_sorted_sw(V, P, dRevJobs, dRevOut, dKeys, dHist, dOrder, nRev, "sw_rev", stream, err, tb, te, hRev, dPosScore);    // (rev job r = survivor r: same score)
+    uint32_t nRevJobs = nRev;
+    if (!filtered) {
+        hipLaunchKernelGGL(rev_jobs_kernel<false>, dim3((nRev + 255) / 256), dim3(256), 0, stream, dPosJobs, dPosOut, dRevPair, dOut, nRev, dRevJobs, dKeys, dHist, dCount + 2,   // (bin_scan cleared the histogram)
+                           (const SwJob *) nullptr, F, (SwOut *) nullptr, (uint32_t *) nullptr);
+        ACHK(hipGetLastError());
+    } else {
+        // coverage gate: the survivors that can still reach the threshold, counted on the device (dCount[3])
+        hipLaunchKernelGGL(rev_jobs_kernel<true>, dim3((nRev + 255) / 256), dim3(256), 0, stream, dPosJobs, dPosOut, dRevPair, dOut, nRev, dRevJobs, dKeys, dHist, dCount + 2,
+                           (const SwJob *) dJobs, F, dRevOut, dCount + 3);
+        ACHK(hipGetLastError());
+        ACHK(hipMemcpyAsync(hCount + 3, dCount + 3, 4, hipMemcpyDeviceToHost, stream));
+        ACHK(sync_wait(stream, "wait_align"));
+        nRevJobs = hCount[3];
+        if (nRevJobs > nRev) { err = "internal: the coverage gate kept more survivors than it was given"; return MK_ERR_DEVICE; }
+    }
+    rc = run_sorted_sw(V, P, dRevJobs, dRevOut, dKeys, dHist, dOrder, nRevJobs, "sw_rev", stream, err, tb, te, hRev, dPosScore);    // (a rev job writes to its survivor's slot: same score)
     if (rc != MK_OK) return rc;
     // collect: the survivors are numbered in pair order
     AlnRaw *dRaw = (AlnRaw *) dev_scratch("align_raw", (size_t) nRev * sizeof(AlnRaw));
@@ -928,7 +1038,7 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
         AV.revWork = dWork;
         AV.raw = dRaw; AV.n = nRev; AV.hitOff = dHitOff; AV.hits = dHits; AV.nq = V.n_queries; AV.q_off = V.q_off; AV.t_off = V.t_off;
         AV.evalTab = dEval; AV.lenIdx = dLenIdx; AV.maxLen = (uint32_t) T.lenIdx.size() - 1; AV.smax = T.smax; AV.bitScore = dBit; AV.sortKey = assemble->dSortKey;
-        AV.evalThr = P.evalue_thr; AV.minAlnLen = P.min_aln_len; AV.tmp = dTmp; AV.pass = dPass; AV.flags = dFlags;
+        AV.evalThr = P.evalue_thr; AV.minAlnLen = P.min_aln_len; AV.filter = F; AV.tmp = dTmp; AV.pass = dPass; AV.flags = dFlags;
         th = tb("align_assemble", (double) nRev * (sizeof(AlnRaw) + 2.0 * sizeof(mk_alignment)), 0);
         hipLaunchKernelGGL(assemble_kernel, dim3((nRev + 255) / 256), dim3(256), 0, stream, AV);
         hipLaunchKernelGGL(assemble_count_kernel, dim3((V.n_queries + 255) / 256), dim3(256), 0, stream, AV, dCnt);
@@ -967,6 +1077,15 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
     }
     ACHK(hipMemcpyAsync(hRaw, dRaw, (size_t) nRev * sizeof(AlnRaw), hipMemcpyDeviceToHost, stream));
     ACHK(hipMemcpyAsync(hCount, dCount, 12, hipMemcpyDeviceToHost, stream));
+    if (filtered) {
+        // the records name pairs of the compacted hit list: the caller's assembly reads it too
+        uint64_t *hOffCut = (uint64_t *) pinned_scratch("align_hitoff_cut_h", ((size_t) V.n_queries + 1) * sizeof(uint64_t));
+        mk_hit *hHitsCut = (mk_hit *) pinned_scratch("align_hits_cut_h", (size_t) n * sizeof(mk_hit));
+        ANULL(hOffCut); ANULL(hHitsCut);
+        ACHK(hipMemcpyAsync(hOffCut, dHitOff, ((size_t) V.n_queries + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        ACHK(hipMemcpyAsync(hHitsCut, dHits, (size_t) n * sizeof(mk_hit), hipMemcpyDeviceToHost, stream));
+        assemble->hitOffCut = hOffCut; assemble->hitsCut = hHitsCut;
+    }
     ACHK(sync_wait(stream, "wait_align"));
     if (hCount[2] != 0) { err = "internal: the position pass disagrees with the score pass for " + std::to_string(hCount[2]) + " pairs"; return MK_ERR_DEVICE; }
     *out = hRaw; *nOut = nRev;
@@ -980,6 +1099,7 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
             for (int c = 0; c < 2 * SW_NCFG; c++) wl[c] = 0;
 #pragma omp for schedule(static) nowait
             for (uint32_t i = 0; i < nRev; i++) {
+                if (hRaw[i].q_start == ALN_SKIPPED) continue;
                 const uint32_t ql = (uint32_t) hRaw[i].q_end + 1, tl = (uint32_t) hRaw[i].t_end + 1;
                 const int c = sw_cfg_of(ql);
                 wl[2 * c] += (double) tl + 2.0 * ql + sizeof(SwJob) + sizeof(SwOut);

@@ -24,6 +24,9 @@ struct AlignView {
 
 // integer result of one accepted pair (everything else is derived on the host in double/float)
 struct AlnRaw { uint32_t pair; int32_t score, q_end, t_end, q_start, t_start; };
+// q_start of a record without start positions: -2 = the reverse pass found another score (t_start holds it), ALN_SKIPPED = the coverage gate of
+// a result filter dropped the pair before the reverse pass (never accepted)
+constexpr int32_t ALN_SKIPPED = -3;
 
 // e-value gate as a per-query-length table: pass(score) = score >= s0 || bit(score) for score < 256
 // (ssw_align_private's `evalue > evalueThr` early return, StripedSmithWaterman.cpp:390-398)
@@ -53,6 +56,11 @@ struct AssembleArgs {
     size_t nOut = 0;                             // records written at the reserved destination
     bool done = false;                           // false after the call: a score beyond the table, the caller assembles from AlnRaw
     double revWork[2 * 16] = {0};                // reverse-pass work per tile configuration (bytes, cells), statistics
+    // a result filter is set (mk_filters.hpp): the stage works on a copy of the hit list without the pairs that fail the length test.  The AlnRaw
+    // records of a range that was not assembled on the device (done == false) name pairs of THAT list: its offsets and hits, pinned scratch
+    // valid until the next call (null without a filter: the caller's own list)
+    uint64_t cutPairs = 0;                       // pairs that went into the score pass
+    const uint64_t *hitOffCut = nullptr; const mk_hit *hitsCut = nullptr;
 };
 
 // pairs = (query of pair p is the one whose hitOff range contains p, target hits[p].seq_id); hits on the host.

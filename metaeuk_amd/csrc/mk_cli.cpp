@@ -55,14 +55,14 @@ const Flag FLAGS[] = {
     {"-s", "4", true}, {"-k", "0", false}, {"--k-score", "seq:2147483647,prof:2147483647", true},
     {"--target-search-mode", "0", false}, {"--alph-size", "aa:21,nucl:5", false}, {"--max-seq-len", "65535", false},
     {"--max-seqs", "300", true}, {"--split", "0", false}, {"--split-mode", "2", false}, {"--split-memory-limit", "0", false},
-    {"-c", "0", false}, {"--cov-mode", "0", false}, {"--comp-bias-corr", "1", true}, {"--comp-bias-corr-scale", "1", true},
+    {"-c", "0", true}, {"--cov-mode", "0", true}, {"--comp-bias-corr", "1", true}, {"--comp-bias-corr-scale", "1", true},
     {"--diag-score", "1", false}, {"--exact-kmer-matching", "0", false}, {"--mask", "1", true}, {"--mask-prob", "0.9", true},
     {"--mask-lower-case", "0", false}, {"--mask-n-repeat", "0", false}, {"--min-ungapped-score", "15", true},
     {"--add-self-matches", "0", false}, {"--spaced-kmer-mode", "1", false}, {"--spaced-kmer-pattern", "", false},
     {"--local-tmp", "", false}, {"--db-load-mode", "0", false}, {"--pca", "", false}, {"--pcb", "", false},
     {"--taxon-list", "", false}, {"--threads", "", true}, {"--compressed", "0", false}, {"-v", "3", true},
     {"-a", "0", false}, {"--alignment-mode", "2", false}, {"--alignment-output-mode", "0", true}, {"--wrapped-scoring", "0", false},
-    {"-e", "100", true}, {"--min-seq-id", "0", false}, {"--min-aln-len", "0", true}, {"--seq-id-mode", "0", false},
+    {"-e", "100", true}, {"--min-seq-id", "0", true}, {"--min-aln-len", "0", true}, {"--seq-id-mode", "0", false},
     {"--alt-ali", "0", false}, {"--max-rejected", "2147483647", false}, {"--max-accept", "2147483647", false},
     {"--score-bias", "0", false}, {"--realign", "0", false}, {"--realign-score-bias", "-0.2", false}, {"--realign-max-seqs", "2147483647", false},
     {"--corr-score-weight", "0", false}, {"--gap-open", "aa:11,nucl:5", true}, {"--gap-extend", "aa:1,nucl:2", true}, {"--zdrop", "40", false},
@@ -182,6 +182,13 @@ int fillParams(const Args &a, mk_params &P, int &gpu) {
     if (auto v = get("--mask-prob")) P.mask_prob = (float) atof(v->c_str());
     if (auto v = get("-e")) P.evalue_thr = atof(v->c_str());
     if (auto v = get("--min-aln-len")) P.min_aln_len = atoi(v->c_str());
+    // the result filters of the searchworkflow list: float parameters (Parameters.cpp:74-75,81), their ranges as the reference's patterns have them
+    if (auto v = get("-c")) P.cov_thr = (float) atof(v->c_str());
+    if (auto v = get("--cov-mode")) P.cov_mode = atoi(v->c_str());
+    if (auto v = get("--min-seq-id")) P.seq_id_thr = (float) atof(v->c_str());
+    if (!(P.cov_thr >= 0.0f && P.cov_thr <= 1.0f)) return die("-c %s: the coverage threshold is a fraction between 0 and 1", *get("-c"));
+    if (auto v = get("--cov-mode")) if (v->size() != 1 || (*v)[0] < '0' || (*v)[0] > '5') return die("--cov-mode %s: coverage modes 0 to 5 exist", *v);
+    if (!(P.seq_id_thr >= 0.0f && P.seq_id_thr <= 1.0f)) return die("--min-seq-id %s: the sequence identity threshold is a fraction between 0 and 1", *get("--min-seq-id"));
     if (auto v = get("--gap-open")) P.gap_open = atoi(aaPart(*v).c_str());
     if (auto v = get("--gap-extend")) P.gap_extend = atoi(aaPart(*v).c_str());
     if (auto v = get("--threads")) setenv("OMP_NUM_THREADS", v->c_str(), 0);
@@ -196,6 +203,15 @@ int fillParams(const Args &a, mk_params &P, int &gpu) {
     if (auto v = get("--gpu")) gpu = atoi(v->c_str());
     if (const char *lr = launcherEnv("LOCAL_RANK")) if (!get("--gpu")) gpu = atoi(lr);
     if (P.gap_open != 11 || P.gap_extend != 1) return die("only --gap-open 11 --gap-extend 1 has a hard-coded Gumbel parameter set in the reference (EvalueComputation.h:64-69); other values are not implemented%s");
+    return 0;
+}
+
+// Profile targets / profile queries (the inverted search): the reference swaps the coverage mode there (Search.cpp:370-396), which is not
+// restated -- non-default result filters are refused, flag by flag
+int refuseFiltersForProfiles(const mk_params &P) {
+    if (P.cov_thr > 0.0f) return die("-c: only the default (0) is implemented with profile targets%s");
+    if (P.cov_mode != 0) return die("--cov-mode: only the default (0) is implemented with profile targets%s");
+    if (P.seq_id_thr > 0.0f) return die("--min-seq-id: only the default (0) is implemented with profile targets%s");
     return 0;
 }
 
@@ -592,7 +608,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     const bool profileQueries = (qdb.dbtype & 0xFFFF) == DBTYPE_HMM_PROFILE;      // the modules as searchslicedtargetprofile.sh calls them
     if (!profileQueries && (qdb.dbtype & 0xFFFF) != mk::DBTYPE_AMINO_ACIDS) return die("only amino-acid and profile query databases are implemented%s");
     if (profileQueries && isSearch) return die("search with a profile query DB is not a workflow of the reference: use predictexons with a profile target DB, or prefilter / align / swapresults%s");
-    if (profileQueries) P.profile_search = 1;
+    if (profileQueries) { if (int rc = refuseFiltersForProfiles(P)) return rc; P.profile_search = 1; }
     Shard sh;
     if (int rc = shardOf(a, sh, argc, argv)) return rc;
     beginShard(a.pos[isAlign && !isSearch ? 3 : 2], sh);
@@ -618,6 +634,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         if (f) { if (fread(&t, 4, 1, f) != 1) t = -1; fclose(f); }
         if (t >= 0 && (t & 0xFFFF) == DBTYPE_HMM_PROFILE) {
             if (!isSearch || profileQueries) return die("a profile target database is searched by `search` / `predictexons` (the inverted sliced search), not by %s", isAlign ? "align" : "prefilter");
+            if (int rc = refuseFiltersForProfiles(P)) return rc;
             // Search.cpp:357-399 takes the inverted sliced search only with --exhaustive-search 1 (predictexons sets it itself for profile targets,
             // PredictExons.cpp:22-26); without it the reference runs the target-side k-mer search of searchtargetprofile.sh (:251-257), which is not built
             {
@@ -800,6 +817,7 @@ int cmdSwapResults(int argc, char **argv) {
     mk_params P;
     int gpu = 0;
     if (int rc = fillParams(a, P, gpu)) return rc;
+    P.cov_thr = 0.0f; P.cov_mode = 0; P.seq_id_thr = 0.0f;                  // (the result filters belong to prefilter / align: not read here)
     if (a.opt.find("-e") == a.opt.end()) P.evalue_thr = 0.001;              // Parameters.cpp:2414
     mk::Database qdb, tdb, rdb;
     std::string e = qdb.open(a.pos[0]);
@@ -1202,7 +1220,10 @@ int cmdPredictExons(int argc, char **argv) {
         FILE *f = fopen((a.pos[1] + ".dbtype").c_str(), "rb");
         int32_t t = -1;
         if (f) { if (fread(&t, 4, 1, f) != 1) t = -1; fclose(f); }
-        if (t >= 0 && (t & 0xFFFF) == DBTYPE_HMM_PROFILE) return predictExonsProfileTargets(a, P, X, minLength, contigs, ord, sh, a.pos[2], t0);
+        if (t >= 0 && (t & 0xFFFF) == DBTYPE_HMM_PROFILE) {
+            if (int rc = refuseFiltersForProfiles(P)) return rc;
+            return predictExonsProfileTargets(a, P, X, minLength, contigs, ord, sh, a.pos[2], t0);
+        }
         if (get("--exhaustive-search") && *get("--exhaustive-search") != "0") return die("--exhaustive-search 1 with a sequence target database is not implemented%s");
     }
     if (sh.world > 1) {                                           // this worker's contigs (a contiguous range of the key order)
@@ -1461,6 +1482,7 @@ int cmdCreateIndex(int argc, char **argv) {
     int gpu = 0;
     if (a.opt.find("-s") == a.opt.end()) a.opt["-s"] = "7.5";           // CreateIndex.cpp:114
     if (int rc = fillParams(a, P, gpu)) return rc;
+    P.cov_thr = 0.0f; P.cov_mode = 0; P.seq_id_thr = 0.0f;             // (the result filters belong to prefilter / align: an index is the same with any)
     const double t0 = now();
     mk::Database db;
     const std::string e = db.open(a.pos[0]);

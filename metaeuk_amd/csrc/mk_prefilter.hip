@@ -38,6 +38,7 @@
 //     radix sort + emit   hits ordered by (query, score desc, target asc) -> compact mk_hit array, DMA'd to its
 //                         final place in the batch's pinned result block
 #include "mk_prefilter.hpp"
+#include "mk_filters.hpp"
 #include "mk_host.hpp"
 #include "mk_kernels.hpp"
 #include "mk_enum.hpp"
@@ -2676,6 +2677,8 @@ int run_prefilter(const PrefilterDeviceView &V, const std::vector<uint64_t> &qOf
         return outBlk.reserve(std::max(want, nOut + n + 4096) * sizeof(mk_hit), nOut * sizeof(mk_hit));
     };
     const int maxHits = std::min<int>(P.max_seqs, (int) V.n_targets);
+    const ResultFilter resultFilter = result_filter_of(P);
+    const bool cutByLength = prefilter_cut_active(resultFilter);
     const uint64_t dbSize = V.n_targets;
     const uint32_t QCAP = 1u << 20;                   // queries per chunk (20-bit field of the output sort key)
     // candidates per chunk held in HBM (~44 B each).  Against a database of more than 2^24 targets a fragment leaves 4e4 candidates (60 M proteins): twice
@@ -3177,6 +3180,36 @@ int run_prefilter(const PrefilterDeviceView &V, const std::vector<uint64_t> &qOf
                 else if (!hostHits[r - nRunsDev].empty())
                     std::memcpy(dst + hostDst[r - nRunsDev], hostHits[r - nRunsDev].data(), hostHits[r - nRunsDev].size() * sizeof(mk_hit));
             }
+        }
+        if (cutByLength && nOut > outOff[q0]) {
+            // -c with coverage mode 0, 2 or 5 (Prefiltering.cpp:856-863): the hits whose two lengths cannot reach the threshold leave the finished
+            // lists -- after the selection of the top --max-seqs, the order kept, whichever front end made the list.  One pass over the chunk in
+            // host memory: every list closes its own holes, then the lists move forward
+            PCHK(sync_wait(stream, "wait_prefilter"));                     // the chunk's DMA has landed
+            ScopedHost sh("host_prefilter_covcut");
+            mk_hit *all = (mk_hit *) outBlk.p;
+            std::vector<uint32_t> kept(nqc);
+#pragma omp parallel for schedule(dynamic, 1024)
+            for (uint32_t ql = 0; ql < nqc; ql++) {
+                const size_t qg = (size_t) q0 + ql;
+                const float qLen = static_cast<float>(qOff[qg + 1] - qOff[qg]);
+                uint64_t w = outOff[qg];
+                for (uint64_t h = outOff[qg]; h < outOff[qg + 1]; h++) {
+                    const uint32_t t = all[h].seq_id;
+                    if (can_be_covered(resultFilter.cov_thr, resultFilter.cov_mode, qLen, static_cast<float>(tOff[t + 1] - tOff[t]))) all[w++] = all[h];
+                }
+                kept[ql] = (uint32_t) (w - outOff[qg]);
+            }
+            uint64_t at = outOff[q0];
+            for (uint32_t ql = 0; ql < nqc; ql++) {
+                const size_t qg = (size_t) q0 + ql;
+                const uint64_t from = outOff[qg];                          // (still the uncut start: outOff[qg] is rewritten after the move)
+                if (kept[ql] && at != from) std::memmove(all + at, all + from, (size_t) kept[ql] * sizeof(mk_hit));
+                outOff[qg] = at;
+                at += kept[ql];
+            }
+            outOff[(size_t) q0 + nqc] = at;
+            nOut = at;
         }
         if (hooks.on_chunk) {
             PCHK(sync_wait(stream, "wait_prefilter"));                     // the chunk's DMA has landed
