@@ -99,6 +99,17 @@ typedef struct {
                                  4: query length >= x target length (and <= it), 5: shorter length >= x longer length (Parameters.h:277-282) */
     float seq_id_thr;         /* --min-seq-id  0 .. 1 */
     int pad_;
+    /* --alignment-mode / -a / --seq-id-mode of the searchworkflow flag list (Parameters.cpp; Alignment.cpp:35-37: -a turns the mode into 3).  All 0 =
+     * today's Matcher::SCORE_COV: seq_id is the score-per-column estimate (Matcher.cpp:160-164), aln_len = max(q span, t span) + 1.  Mode 3
+     * (Matcher::SCORE_COV_SEQID) runs the banded backtrace of every alignment that passes the coverage test (SmithWaterman::banded_sw +
+     * computerBacktrace, StripedSmithWaterman.cpp:491-538, 1347-1600): aln_len = length of the backtrace, seq_id = Util::computeSeqId(seq_id_mode,
+     * identical residues, ...) (Util.cpp:532-542, Matcher.cpp:105-113), and --min-seq-id / --min-aln-len test those exact values.  The record
+     * order does not depend on the mode.  Not with profile queries (the PROFILE_SEQ branch of banded_sw is not restated): MK_ERR_UNSUPPORTED. */
+    int alignment_mode;       /* --alignment-mode  0 or 2: score, coverage, estimated identity; 3: exact identity; 1 and 4: MK_ERR_UNSUPPORTED; else MK_ERR_ARG */
+    int add_backtrace;        /* -a                0 or 1 (else MK_ERR_ARG); 1 implies mode 3 and keeps the operation strings (mk_align_backtrace) */
+    int seq_id_mode;          /* --seq-id-mode     0: identities / alignment length, 1: / the shorter sequence, 2: / the longer one (Parameters.h:285-287);
+                                 read in mode 3 only, other values MK_ERR_ARG */
+    int pad2_;
 } mk_params;
 
 /* ---- process-wide ---- */
@@ -108,10 +119,22 @@ void mk_default_params(mk_params *p);       /* defaults of `metaeuk predictexons
 int mk_device_name(char *buf, size_t cap);
 int mk_device_memory(uint64_t *free_bytes, uint64_t *total_bytes);   /* HBM of the bound GPU (the split planner of the commands sizes the target side with it) */
 int mk_host_threads(void);                  /* CPUs usable by this process (affinity and cgroup quota) */
-/* the result filters of `p` on one pair, host code without a GPU: 1 = keep, 0 = drop, MK_ERR_ARG for values outside their range.
+/* the result filters of `p` on one pair, host code without a GPU: 1 = keep, 0 = drop, MK_ERR_ARG for values outside their range
+ * (alignment_mode / add_backtrace / seq_id_mode are checked as every call checks them: MK_ERR_UNSUPPORTED for the modes 1 and 4).
  * a == NULL: the test on the two lengths alone (Util::canBeCovered); else also Util::hasCoverage on a->qcov / a->dbcov and
  * (double) a->seq_id >= (double) p->seq_id_thr.  The host paths of the library decide with it. */
 int mk_result_filter(const mk_params *p, int q_len, int t_len, const mk_alignment *a /* NULL: length test only */);
+
+/* the backtrace of --alignment-mode 3 on one pair, host code without a GPU (the twin the kernel is checked against, and what the host
+ * assembly of the alignment stage runs): SmithWaterman::banded_sw<SEQ_SEQ> + computerBacktrace<SUBSTITUTIONMATRIX> on the rectangle the
+ * pointers START at (q / q_bias8 at q_start, t at t_start; qn = q_end - q_start + 1, tn likewise), mat = 21 x 21 int8 scores [q * 21 + t],
+ * score = the pair's Smith-Waterman score.  The first band is |tn - qn| + 1, doubled while the banded maximum misses the score; *attempts =
+ * band widths tried.  ops (may be NULL; ops_cap >= qn + tn always suffices) receives *bt_len uncompressed operations M / I / D (I consumes a
+ * query residue, D a target residue), *identities the M columns with equal residues.  Returns MK_OK; 1 when the trace left the band or did not
+ * stop on the first cell (no path: *bt_len = *identities = 0 -- the reference reads unwritten memory there); MK_ERR_SW_MISMATCH when the band has
+ * reached max(qn, tn) without the score ("Alignment score and position are not consensus", where the reference exits). */
+int mk_backtrace_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int qn, const uint8_t *t, int tn, int score,
+                      int gap_open, int gap_extend, char *ops, uint32_t ops_cap, uint32_t *bt_len, uint32_t *identities, uint32_t *attempts);
 
 /* ---- encoding: Sequence::mapSequence + SubstitutionMatrix::aa2num (Sequence.cpp:307-324) ---- */
 void mk_encode(const char *ascii, size_t len, uint8_t *codes);
@@ -226,6 +249,10 @@ int mk_prefilter_result_set(mk_queries *q, const mk_hit *hits, const uint64_t *o
  * alignments, in output order, are alns[offsets[i] .. offsets[i+1]). */
 int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *params);
 int mk_align_result(const mk_queries *q, const mk_alignment **alns, const uint64_t **offsets /* n+1 */);
+/* the backtraces of a batch aligned with params->add_backtrace = 1 (mk_align or mk_search): alignment k of mk_align_result has
+ * ops[ops_offsets[k] .. ops_offsets[k+1]), uncompressed M / I / D (empty for a pair without a path), and identities[k] identical residues.
+ * Views owned by the batch handle.  MK_ERR_ARG when the batch was not aligned with add_backtrace. */
+int mk_align_backtrace(const mk_queries *q, const char **ops, const uint64_t **ops_offsets /* n_alignments + 1 */, const uint32_t **identities);
 
 /* ---- producer of the query batch: `extractorfs --translate` as predictexons runs it
  * (util/extractorfs.cpp:19-159, Orf::findAll with orf-start-mode 1, all six frames, genetic code 1, contig start / end mode
@@ -312,6 +339,14 @@ void mk_shutdown(void);
 int mk_sw_pairs(mk_targetdb *db, mk_queries *q, const mk_params *params,
                 const uint32_t *q_idx, const uint32_t *t_idx, uint64_t n_pairs, int with_start,
                 int32_t *out5);
+/* the backtrace kernel on explicit pairs, after mk_sw_pairs(with_start = 1): in5 = what it wrote (score, q_end, t_end, q_start, t_start).  A
+ * pair with score <= 0 or without start positions gets bt_len = identities = attempts = 0.  ops_off[n_pairs + 1] is sized by the caller: at least
+ * (q span + t span) bytes per pair; pair p's operations are ops[ops_off[p] .. ops_off[p] + bt_len[p]).  ops / ops_off may be NULL (counts only);
+ * attempts and final_band (the band of the last attempt) may be NULL.  bt_len[p] = 0 with attempts[p] > 0: the trace left the band.
+ * MK_ERR_SW_MISMATCH for a stalled band, MK_ERR_UNSUPPORTED (size in the message) for a pair whose direction matrix exceeds one launch's scratch. */
+int mk_sw_backtrace_pairs(mk_targetdb *db, mk_queries *q, const mk_params *params, const uint32_t *q_idx, const uint32_t *t_idx, uint64_t n_pairs,
+                          const int32_t *in5, const uint64_t *ops_off, char *ops, uint32_t *bt_len, uint32_t *identities, uint32_t *attempts,
+                          int32_t *final_band);
 /* ungapped diagonal scores (exact, unclamped) for (q_idx, t_idx, diagonal) triples:
  * UngappedAlignment::scoreSingelSequenceByCounterResult (UngappedAlignment.cpp:434-451) */
 int mk_ungapped(mk_targetdb *db, mk_queries *q, const uint32_t *q_idx, const uint32_t *t_idx,
@@ -332,6 +367,13 @@ size_t mk_format_alignment(char *buf, const mk_alignment *a);
  * 0 when cap is too small (32 B per hit, 160 B per alignment always suffice). */
 size_t mk_format_hits(char *buf, size_t cap, const mk_hit *hits, uint64_t n, const uint32_t *target_keys);
 size_t mk_format_alignments(char *buf, size_t cap, const mk_alignment *alns, uint64_t n);
+/* the 11-column line of -a: the 10 columns, a tab and Matcher::compressAlignment of the n_ops operations (run lengths, "12M3I20M";
+ * Matcher.cpp:166-185, 312-317).  At most 160 + 11 * runs + 2 bytes; a run costs at most 11 bytes and there are at most n_ops runs. */
+size_t mk_format_alignment_bt(char *buf, const mk_alignment *a, const char *ops, uint64_t n_ops);
+/* bulk form: alns[0..n) with their operations ops[ops_offsets[k] .. ops_offsets[k+1]) (what mk_align_backtrace returns).  Returns the bytes
+ * written; 0 when cap is too small: 160 * n + 3 * ops_offsets[n] + 16 * n bytes always suffice (a run of r operations prints at most
+ * 1 + digits(r) <= 3 r bytes). */
+size_t mk_format_alignments_bt(char *buf, size_t cap, const mk_alignment *alns, uint64_t n, const char *ops, const uint64_t *ops_offsets);
 
 #ifdef __cplusplus
 }

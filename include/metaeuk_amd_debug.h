@@ -31,6 +31,10 @@ int mk_synth_write_seqdb(const char *base, const uint8_t *residues, const uint64
 /* sizeof(mk_params) of this build: a binding that mirrors the struct (metaeuk_amd/api.py) checks its own layout against it */
 size_t mk_debug_params_size(void);
 
+/* pairs of the batch's last mk_align / mk_search in --alignment-mode 3 whose trace left the band or did not stop on the first cell (they get no
+ * backtrace: aln_len stays the mode-2 value, 0 identities -- DESIGN.md, the backtrace stage); the tests assert 0 on their inputs */
+uint64_t mk_debug_trace_left_band(const mk_queries *q);
+
 /* ---- experiment hook (tools/micro/mk_experiments.hip is its only user): the device view of a (database, batch) pair -- a
  * mk::PrefilterDeviceView (metaeuk_amd/csrc/mk_prefilter.hpp: pointers into HBM, valid while both handles live) copied into view_out, whose
  * size must be given as view_bytes -- and the batch's host offsets.  The layout of that struct is NOT stable across builds. */

@@ -20,7 +20,8 @@ class Params(C.Structure):
                 ("evalue_thr", C.c_double), ("min_aln_len", C.c_int), ("simd_lanes_byte", C.c_int),
                 ("simd_lanes_word", C.c_int), ("simd_lanes_double", C.c_int), ("host_l2_bytes", C.c_uint64),
                 ("profile_search", C.c_int), ("kmer_size", C.c_int),
-                ("cov_thr", C.c_float), ("cov_mode", C.c_int), ("seq_id_thr", C.c_float), ("pad_", C.c_int)]   # -c, --cov-mode, --min-seq-id
+                ("cov_thr", C.c_float), ("cov_mode", C.c_int), ("seq_id_thr", C.c_float), ("pad_", C.c_int),   # -c, --cov-mode, --min-seq-id
+                ("alignment_mode", C.c_int), ("add_backtrace", C.c_int), ("seq_id_mode", C.c_int), ("pad2_", C.c_int)]   # --alignment-mode, -a, --seq-id-mode
 
 
 class Hit(C.Structure):
@@ -50,7 +51,8 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_profiles_create", "mk_profiles_derived", "mk_swap_alignments", "mk_swapped_result", "mk_swapped_destroy",
            "mk_targetdb_masked_residues", "mk_targetdb_kmer_size", "mk_targetdb_longest_list", "mk_targetdb_index_compare",
            "mk_synth_targets", "mk_synth_fragments", "mk_synth_seqdb", "mk_synth_write_seqdb", "mk_targetdb_create_sequences", "mk_prefilter_statistics",
-           "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size"]
+           "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size",
+           "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band"]
 
 
 def lib():
@@ -72,6 +74,9 @@ def lib():
         L.mk_format_orf_header.restype = C.c_size_t
         L.mk_format_prediction_exon.restype = C.c_size_t
         L.mk_debug_params_size.restype = C.c_size_t
+        L.mk_format_alignment_bt.restype = C.c_size_t
+        L.mk_format_alignments_bt.restype = C.c_size_t
+        L.mk_debug_trace_left_band.restype = C.c_uint64
         _LIB = L
     return _LIB
 
@@ -567,6 +572,72 @@ def sw_pairs(db, q, q_idx, t_idx, with_start=True, params=None):
     out = np.zeros((len(q_idx), 5), dtype=np.int32)
     _chk(lib().mk_sw_pairs(db.h, q.h, C.byref(p), _p(q_idx), _p(t_idx), C.c_uint64(len(q_idx)), C.c_int(1 if with_start else 0), _p(out)))
     return out
+
+
+def backtrace_host(mat, q, bias8, t, score, gap_open=11, gap_extend=1):
+    """the backtrace of --alignment-mode 3 on one rectangle, host code (mk_backtrace_host): mat = int8 [21, 21] scores [q, t], q / t = uint8 codes of
+    the rectangle, bias8 = the query's int8 composition bias over it -> (ops bytes or None when the trace left the band, identities, attempts)"""
+    mat = np.ascontiguousarray(mat, dtype=np.int8); q = np.ascontiguousarray(q, dtype=np.uint8)
+    t = np.ascontiguousarray(t, dtype=np.uint8); bias8 = np.ascontiguousarray(bias8, dtype=np.int8)
+    ops = np.zeros(len(q) + len(t), dtype=np.uint8)
+    n, ids, att = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = lib().mk_backtrace_host(_p(mat), _p(q), _p(bias8), C.c_int(len(q)), _p(t), C.c_int(len(t)), C.c_int(int(score)), C.c_int(gap_open),
+                                 C.c_int(gap_extend), _p(ops), C.c_uint32(ops.size), C.byref(n), C.byref(ids), C.byref(att))
+    if rc < 0:
+        _chk(rc)
+    return (ops[:n.value].tobytes() if rc == 0 else None), int(ids.value), int(att.value)
+
+
+def sw_backtrace_pairs(db, q, q_idx, t_idx, in5, params=None, keep_ops=True):
+    """the backtrace kernel on the pairs of sw_pairs(with_start=True) -> (list of ops bytes or None, bt_len u32, identities u32, attempts u32,
+    final band i32)"""
+    p = params or db.params
+    q_idx = np.ascontiguousarray(q_idx, dtype=np.uint32)
+    t_idx = np.ascontiguousarray(t_idx, dtype=np.uint32)
+    in5 = np.ascontiguousarray(in5, dtype=np.int32)
+    n = len(q_idx)
+    span = np.where(in5[:, 3] >= 0, (in5[:, 1] - in5[:, 3] + 1) + (in5[:, 2] - in5[:, 4] + 1), 0).astype(np.uint64)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(span, dtype=np.uint64)
+    ops = np.zeros(max(1, int(off[-1])), dtype=np.uint8)
+    bt = np.zeros(n, dtype=np.uint32); ids = np.zeros(n, dtype=np.uint32); att = np.zeros(n, dtype=np.uint32); band = np.zeros(n, dtype=np.int32)
+    _chk(lib().mk_sw_backtrace_pairs(db.h, q.h, C.byref(p), _p(q_idx), _p(t_idx), C.c_uint64(n), _p(in5), _p(off) if keep_ops else None,
+                                     _p(ops) if keep_ops else None, _p(bt), _p(ids), _p(att), _p(band)))
+    strings = [ops[int(off[k]):int(off[k]) + int(bt[k])].tobytes() for k in range(n)] if keep_ops else None
+    return strings, bt, ids, att, band
+
+
+def align_backtrace(q, n_alignments):
+    """the backtraces of a batch aligned with add_backtrace = 1 -> (ops bytes, offsets uint64[n_alignments + 1], identities uint32[n_alignments])"""
+    op, fp, ip = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _chk(lib().mk_align_backtrace(q.h, C.byref(op), C.byref(fp), C.byref(ip)))
+    off = np.array(np.ctypeslib.as_array(C.cast(fp, C.POINTER(C.c_uint64)), shape=(n_alignments + 1,)))
+    ids = np.array(np.ctypeslib.as_array(C.cast(ip, C.POINTER(C.c_uint32)), shape=(n_alignments,))) if n_alignments else np.zeros(0, dtype=np.uint32)
+    return (C.string_at(op, int(off[-1])) if int(off[-1]) else b""), off, ids
+
+
+def trace_left_band(q):
+    """test hook: pairs of the batch's last mode-3 alignment whose trace left the band (they carry no backtrace)"""
+    return int(lib().mk_debug_trace_left_band(q.h))
+
+
+def format_alignment_bt(aln, ops):
+    """the 11-column line of -a for one alignment and its uncompressed operations"""
+    buf = C.create_string_buffer(192 + 12 * max(1, len(ops)))
+    n = lib().mk_format_alignment_bt(buf, C.byref(aln), C.c_char_p(bytes(ops)), C.c_uint64(len(ops)))
+    return buf.raw[:n]
+
+
+def format_alignments_bt_bulk(alns, lo, hi, ops, ops_off):
+    """bytes of the 11-column lines of alns[lo:hi] with the operations of align_backtrace"""
+    n = hi - lo
+    if n <= 0:
+        return b""
+    ops_off = np.ascontiguousarray(ops_off, dtype=np.uint64)
+    buf = np.empty(176 * n + 3 * int(ops_off[hi]), dtype=np.uint8)
+    w = lib().mk_format_alignments_bt(_p(buf), C.c_size_t(buf.size), C.c_void_p(C.addressof(alns) + lo * C.sizeof(Alignment)), C.c_uint64(n),
+                                      C.c_char_p(ops), _p(ops_off[lo:]))
+    return buf[:w].tobytes()
 
 
 def ungapped(db, q, q_idx, t_idx, diag):

@@ -13,6 +13,7 @@
 #include "mk_index.hpp"
 #include "mk_prefilter.hpp"
 #include "mk_profile.hpp"
+#include "mk_trace.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -307,6 +308,10 @@ struct mk_queries {
     mk::HostBlock hits; size_t nHits = 0; std::vector<uint64_t> hitOff; bool havePref = false;
     mk::PrefilterStats pfStats;      // run statistics of the prefilter over this batch (Prefiltering.cpp:889-904)
     mk::HostBlock alns; std::vector<uint64_t> alnOff; bool haveAln = false;
+    // the backtraces of a batch aligned with add_backtrace (mk_align_backtrace): operations of alignment k = btOps[btOff[k] .. btOff[k+1]), in the
+    // order of `alns`; appended chunk by chunk like the alignments (align_range, after wait_turn)
+    std::vector<char> btOps; std::vector<uint64_t> btOff; std::vector<uint32_t> btIds; bool haveBt = false;
+    uint64_t btLeftBand = 0;         // pairs of the last alignment whose trace left the band (no path)
     struct SearchJob *job = nullptr; // mk_search_begin: the search in flight over this batch (mk_search_wait clears it)
     // (the profile images too -- ADVICE round 5: a hipFree of theirs in mk_queries_destroy synchronised the device under the batch in flight)
     mk_queries() { dRes.pooled = dOff.pooled = dKmerThr.pooled = dCorr.pooled = dBias8.pooled = dProfSorted.pooled = dProfAln.pooled = true; }
@@ -512,6 +517,7 @@ void mk_default_params(mk_params *p) {
     p->profile_search = 0;
     p->kmer_size = 0;
     p->cov_thr = 0.0f; p->cov_mode = 0; p->seq_id_thr = 0.0f; p->pad_ = 0;
+    p->alignment_mode = 0; p->add_backtrace = 0; p->seq_id_mode = 0; p->pad2_ = 0;
 }
 
 size_t mk_debug_params_size(void) { return sizeof(mk_params); }
@@ -527,10 +533,40 @@ static int check_filters(const mk_params *P, bool profiles) {
     return MK_OK;
 }
 
+// --alignment-mode / -a / --seq-id-mode of a call: values in range; mode 3 not for profile queries (the PROFILE_SEQ branch of banded_sw and the
+// I / D exchange of swapResult are not restated)
+static bool trace_mode(const mk_params *P) { return P->alignment_mode == mk::ALIGNMENT_MODE_SCORE_COV_SEQID || P->add_backtrace == 1; }
+static int check_alignment_mode(const mk_params *P, bool profiles) {
+    if (P->alignment_mode == 1 || P->alignment_mode == 4)
+        return fail(MK_ERR_UNSUPPORTED, "--alignment-mode %d is not implemented (2: score, coverage and estimated identity; 3: exact identity from the backtrace)", P->alignment_mode);
+    if (P->alignment_mode != 0 && P->alignment_mode != 2 && P->alignment_mode != 3)
+        return fail(MK_ERR_ARG, "--alignment-mode %d out of range (0 to 4)", P->alignment_mode);
+    if (P->add_backtrace != 0 && P->add_backtrace != 1) return fail(MK_ERR_ARG, "-a %d out of range (0 or 1)", P->add_backtrace);
+    if (trace_mode(P) && (P->seq_id_mode < 0 || P->seq_id_mode > 2)) return fail(MK_ERR_ARG, "--seq-id-mode %d out of range (0 to 2)", P->seq_id_mode);
+    if (profiles && trace_mode(P))
+        return fail(MK_ERR_UNSUPPORTED, "--alignment-mode 3 / -a with profile queries (the inverted search of a profile target database) are not implemented");
+    return MK_OK;
+}
+
+int mk_backtrace_host(const int8_t *mat, const uint8_t *q, const int8_t *bias8, int qn, const uint8_t *t, int tn, int score, int gapOpen, int gapExtend,
+                      char *ops, uint32_t opsCap, uint32_t *btLen, uint32_t *identities, uint32_t *attempts) {
+    if (!mat || !q || !bias8 || !t || qn <= 0 || tn <= 0) return fail(MK_ERR_ARG, "mk_backtrace_host: null argument or empty rectangle");
+    if (ops && (uint64_t) opsCap < (uint64_t) qn + (uint64_t) tn) return fail(MK_ERR_ARG, "mk_backtrace_host: ops_cap %u below qn + tn = %llu", opsCap, (unsigned long long) qn + (unsigned long long) tn);
+    mk::TraceResult r;
+    const int st = mk::trace_host(mat, q, bias8, qn, t, tn, score, gapOpen, gapExtend, ops, opsCap, &r);
+    if (btLen) *btLen = r.bt_len;
+    if (identities) *identities = r.identities;
+    if (attempts) *attempts = r.attempts;
+    if (st == mk::TRACE_STALLED)
+        return fail(MK_ERR_SW_MISMATCH, "Alignment score and position are not consensus: a %d x %d rectangle misses its score %d at band %d", qn, tn, score, r.band);
+    return st == mk::TRACE_OK ? MK_OK : 1;
+}
+
 int mk_result_filter(const mk_params *p, int q_len, int t_len, const mk_alignment *a) {
     if (!p) return fail(MK_ERR_ARG, "null argument");
-    const int rc = check_filters(p, false);
+    int rc = check_filters(p, false);
     if (rc != MK_OK) return rc;
+    if ((rc = check_alignment_mode(p, false)) != MK_OK) return rc;
     if (!mk::can_be_covered(p->cov_thr, p->cov_mode, static_cast<float>(q_len), static_cast<float>(t_len))) return 0;
     if (a && !(mk::has_coverage(p->cov_thr, p->cov_mode, a->qcov, a->dbcov) && mk::seq_id_ok(a->seq_id, p->seq_id_thr))) return 0;
     return 1;
@@ -576,6 +612,7 @@ static int targetdb_create(const uint8_t *residues, const uint64_t *offsets, uin
     // IndexTable::computeKmerSize (IndexTable.h:439-449): from 3.35e9 target residues on the reference searches with k = 7
     if (P->kmer_size != 0 && P->kmer_size != 6 && P->kmer_size != 7) return fail(MK_ERR_UNSUPPORTED, "-k %d: k-mer sizes 6 and 7 are implemented", P->kmer_size);
     if ((rc = check_filters(P, P->profile_search != 0)) != MK_OK) return rc;
+    if ((rc = check_alignment_mode(P, P->profile_search != 0)) != MK_OK) return rc;
     const int kmerSize = prebuilt ? prebuilt->kmerSize : (P->kmer_size ? P->kmer_size : (offsets[n] < 3350000000ull ? 6 : 7));
     if (prebuilt && P->kmer_size && P->kmer_size != kmerSize) return fail(MK_ERR_ARG, "-k %d, but the index DB was built with k = %d", P->kmer_size, kmerSize);
     mk_targetdb *db = new mk_targetdb();
@@ -1303,6 +1340,50 @@ int mk_sw_pairs(mk_targetdb *db, mk_queries *q, const mk_params *P, const uint32
     return MK_OK;
 }
 
+// the backtrace kernel on explicit pairs (mk_trace.hip), after mk_sw_pairs(with_start)
+int mk_sw_backtrace_pairs(mk_targetdb *db, mk_queries *q, const mk_params *P, const uint32_t *qIdx, const uint32_t *tIdx, uint64_t n, const int32_t *in5,
+                          const uint64_t *opsOff, char *ops, uint32_t *btLen, uint32_t *identities, uint32_t *attempts, int32_t *finalBand) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P || !qIdx || !tIdx || !in5 || !btLen || !identities) return fail(MK_ERR_ARG, "null argument");
+    if ((ops == nullptr) != (opsOff == nullptr)) return fail(MK_ERR_ARG, "mk_sw_backtrace_pairs: ops and ops_off go together");
+    if (q->isProfile || db->profileSearch) return fail(MK_ERR_UNSUPPORTED, "the backtrace of profile queries is not implemented");
+    std::vector<mk::TracePair> pairs;
+    std::vector<uint64_t> who, off(1, 0);
+    for (uint64_t p = 0; p < n; p++) {
+        btLen[p] = 0; identities[p] = 0;
+        if (attempts) attempts[p] = 0;
+        if (finalBand) finalBand[p] = 0;
+        if (qIdx[p] >= q->n || tIdx[p] >= db->n) return fail(MK_ERR_ARG, "pair %llu out of range", (unsigned long long) p);
+        const int32_t *r = in5 + p * 5;
+        if (r[0] <= 0 || r[3] < 0 || r[4] < 0) continue;
+        const int64_t qLen = (int64_t) (q->off[qIdx[p] + 1] - q->off[qIdx[p]]), tLen = (int64_t) (db->off[tIdx[p] + 1] - db->off[tIdx[p]]);
+        if (r[1] < r[3] || r[2] < r[4] || r[1] >= qLen || r[2] >= tLen) return fail(MK_ERR_ARG, "pair %llu: coordinates outside its sequences", (unsigned long long) p);
+        mk::TracePair tp;
+        tp.q_pos = q->off[qIdx[p]] + (uint64_t) r[3]; tp.t_pos = db->off[tIdx[p]] + (uint64_t) r[4];
+        tp.qn = r[1] - r[3] + 1; tp.tn = r[2] - r[4] + 1; tp.score = r[0];
+        if (opsOff && opsOff[p + 1] - opsOff[p] < (uint64_t) tp.qn + (uint64_t) tp.tn)
+            return fail(MK_ERR_ARG, "pair %llu: its ops region holds %llu bytes, q span + t span = %d", (unsigned long long) p, (unsigned long long) (opsOff[p + 1] - opsOff[p]), tp.qn + tp.tn);
+        pairs.push_back(tp); who.push_back(p);
+        off.push_back(off.back() + (uint64_t) tp.qn + (uint64_t) tp.tn);
+    }
+    std::vector<mk::TraceResult> res(pairs.size());
+    std::vector<char> buf(ops ? off.back() : 0);
+    std::string err;
+    rc = mk::run_trace_device(q->dRes.p, q->dBias8.p, db->dRes.p, db->dMatAln.p, pairs.data(), pairs.size(), P->gap_open, P->gap_extend, ops != nullptr,
+                              off.data(), buf.data(), g_stream, res.data(), err, timed_begin, timed_end);
+    timed_flush();
+    if (rc != MK_OK) return fail(rc, "%s", err.c_str());
+    for (size_t k = 0; k < pairs.size(); k++) {
+        const uint64_t p = who[k];
+        btLen[p] = res[k].bt_len; identities[p] = res[k].identities;
+        if (attempts) attempts[p] = res[k].attempts;
+        if (finalBand) finalBand[p] = res[k].band;
+        if (ops && res[k].bt_len) std::memcpy(ops + opsOff[p], buf.data() + off[k], res[k].bt_len);
+    }
+    return MK_OK;
+}
+
 int mk_ungapped(mk_targetdb *db, mk_queries *q, const uint32_t *qIdx, const uint32_t *tIdx, const uint16_t *diag, uint64_t n, int32_t *outScores) {
     int rc = ensure_ready();
     if (rc) return rc;
@@ -1498,7 +1579,9 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
     // serves a range in which a score lies beyond the e-value table
     mk::AssembleArgs asmArgs;
     static const bool hostAssemble = mk::knob_long("MK_ALIGN_HOST_ASSEMBLE", 0) != 0;
-    asmArgs.tables = hostAssemble ? nullptr : tables;
+    // --alignment-mode 3 / -a: the backtrace stage (mk_trace.hip) runs between the reverse pass and the assembly, and the assembly on the host
+    const bool mode3 = trace_mode(P), keepOps = P->add_backtrace == 1;
+    asmArgs.tables = hostAssemble || mode3 ? nullptr : tables;
     asmArgs.dSortKey = db->dKeys.p;
     asmArgs.counts = (uint32_t *) mk::pinned_scratch(stream == g_stream2 ? "asm_counts_h2" : "asm_counts_h", std::max<size_t>(nqc, 1) * 4);
     if (!asmArgs.counts) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
@@ -1512,8 +1595,8 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
     int rc = mk::run_align_device(V, hitOff.data(), hits, n, gate, *P, stream, nullptr, &raw, &m, err, timed_begin, timed_end, timed_set, &asmArgs);
     timed_flush();
     if (rc != MK_OK) return fail(rc, "%s", err.c_str());
-    turn();
     if (asmArgs.done) {
+        turn();
         uint64_t o = 0;
         for (uint32_t i = 0; i < nqc; i++) { o += asmArgs.counts[i]; q->alnOff[(size_t) q0 + i + 1] = nAlnOut + o; }
         nAlnOut += asmArgs.nOut;
@@ -1531,6 +1614,45 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
         while (lo < hi) { const size_t mid = (lo + hi) >> 1; if (raw[mid].pair < want) lo = mid + 1; else hi = mid; }
         first[i] = lo;
     }
+    // mode 3: a trace job for every record the reference does not return early on (StripedSmithWaterman.cpp:485-489)
+    std::vector<int64_t> jobOf;                        // record -> its trace job (-1: none)
+    std::vector<mk::TraceResult> tres;
+    std::vector<uint64_t> topsOff;
+    std::vector<char> tops;
+    if (mode3) {
+        std::vector<mk::TracePair> tp;
+        jobOf.assign(m, -1);
+        topsOff.assign(1, 0);
+        for (uint32_t i = 0; i < nqc; i++) {
+            const uint64_t qOff = q->off[(size_t) q0 + i];
+            const unsigned qLen = (unsigned) (q->off[(size_t) q0 + i + 1] - qOff);
+            for (uint64_t k = first[i]; k < first[i + 1]; k++) {
+                const mk::AlnRaw &r = raw[k];
+                if (r.q_start == mk::ALN_SKIPPED || r.q_start == -2) continue;
+                const uint32_t t = hits[r.pair].seq_id;
+                const unsigned tLen = (unsigned) (db->off[t + 1] - db->off[t]);
+                if (!mk::has_coverage(P->cov_thr, P->cov_mode, mk::compute_cov((unsigned) r.q_start, (unsigned) r.q_end, qLen),
+                                      mk::compute_cov((unsigned) r.t_start, (unsigned) r.t_end, tLen))) continue;
+                mk::TracePair x;
+                x.q_pos = qOff + (uint64_t) r.q_start; x.t_pos = db->off[t] + (uint64_t) r.t_start;
+                x.qn = r.q_end - r.q_start + 1; x.tn = r.t_end - r.t_start + 1; x.score = r.score;
+                jobOf[k] = (int64_t) tp.size();
+                tp.push_back(x);
+                if (keepOps) topsOff.push_back(topsOff.back() + (uint64_t) x.qn + (uint64_t) x.tn);
+            }
+        }
+        tres.resize(tp.size());
+        if (keepOps) tops.resize(topsOff.back());
+        mk::TraceStageStats st;
+        rc = mk::run_trace_device(q->dRes.p, q->dBias8.p, db->dRes.p, db->dMatAln.p, tp.data(), tp.size(), P->gap_open, P->gap_extend, keepOps, topsOff.data(),
+                                  tops.data(), stream, tres.data(), err, timed_begin, timed_end, &st);
+        timed_flush();
+        if (rc != MK_OK) return fail(rc, "%s", err.c_str());
+        turn();
+        q->btLeftBand += st.leftBand;
+    }
+    turn();
+    std::vector<uint32_t> src(mode3 ? m : 0);          // mode 3: the record behind every kept alignment
     // records are written at their upper-bound position; rejected ones (rare) leave holes that are closed afterwards
     if (!q->alns.reserve(std::max<size_t>(nAlnOut + m, 1) * sizeof(mk_alignment), nAlnOut * sizeof(mk_alignment))) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
     mk_alignment *alns = (mk_alignment *) q->alns.p + nAlnOut;
@@ -1561,10 +1683,30 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
             float sid = (s16 / static_cast<float>(std::max(qAln, dbAln))) * 0.1656 + 0.1141;   // Matcher.cpp:160-164
             sid = std::min(sid, 1.0f);
             a.seq_id = std::max(0.0f, sid);
+            if (mode3) {                                      // Matcher.cpp:105-113: the backtrace's length when there is one, the exact identity
+                const mk::TraceResult *T = jobOf[k] >= 0 ? &tres[(size_t) jobOf[k]] : nullptr;
+                const bool path = T && T->status == mk::TRACE_OK && T->bt_len > 0;
+                if (path) a.aln_len = (int32_t) T->bt_len;
+                a.seq_id = mk::compute_seq_id(P->seq_id_mode, path ? (int) T->identities : 0, qLen, tLen, a.aln_len);
+            }
             a.bit_score = static_cast<int>(db->evaluer.bitScore((double) r.score) + 0.5);
-            if (a.evalue <= P->evalue_thr && a.aln_len >= P->min_aln_len && mk_result_filter(P, qLen, tLen, &a) == 1) alns[w++] = a;
+            if (a.evalue <= P->evalue_thr && a.aln_len >= P->min_aln_len && mk_result_filter(P, qLen, tLen, &a) == 1) {
+                if (mode3) src[w] = (uint32_t) k;
+                alns[w++] = a;
+            }
         }
-        if (w - begin > 1) {
+        if (mode3 && w - begin > 1) {                         // the same order, the records' sources carried along
+            std::vector<uint32_t> perm((size_t) (w - begin));
+            for (size_t x = 0; x < perm.size(); x++) perm[x] = (uint32_t) x;
+            std::sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
+                mk_alignment kx = alns[begin + x], ky = alns[begin + y];
+                if (!db->keys.empty()) { kx.db_key = db->keys[kx.db_key]; ky.db_key = db->keys[ky.db_key]; }
+                return mk::alignment_less(kx, ky);
+            });
+            std::vector<mk_alignment> ta(alns + begin, alns + w);
+            std::vector<uint32_t> tsrc(src.begin() + (ptrdiff_t) begin, src.begin() + (ptrdiff_t) w);
+            for (size_t x = 0; x < perm.size(); x++) { alns[begin + x] = ta[perm[x]]; src[begin + x] = tsrc[perm[x]]; }
+        } else if (w - begin > 1) {
             if (db->keys.empty()) std::sort(alns + begin, alns + w, mk::alignment_less);
             else std::sort(alns + begin, alns + w, [&](const mk_alignment &x, const mk_alignment &y) {      // Matcher::compareHits ties on the DB key
                 mk_alignment kx = x, ky = y; kx.db_key = db->keys[x.db_key]; ky.db_key = db->keys[y.db_key];
@@ -1578,8 +1720,19 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
     uint64_t o = 0;                                    // range-local offsets
     for (uint32_t i = 0; i < nqc; i++) {
         if (holes && cnt[i] && o != first[i]) std::memmove(alns + o, alns + first[i], (size_t) cnt[i] * sizeof(mk_alignment));   // blocks only move forward
+        if (mode3 && holes && cnt[i] && o != first[i]) std::memmove(src.data() + o, src.data() + first[i], (size_t) cnt[i] * sizeof(uint32_t));
         o += cnt[i];
         q->alnOff[(size_t) q0 + i + 1] = nAlnOut + o;
+    }
+    if (keepOps) {                                     // the strings in the order of the alignments (the chunk's turn: appended in chunk order)
+        if (q->btOff.empty()) q->btOff.push_back(0);
+        for (uint64_t x = 0; x < o; x++) {
+            const int64_t j = jobOf[src[x]];
+            const bool path = j >= 0 && tres[(size_t) j].status == mk::TRACE_OK;
+            if (path) q->btOps.insert(q->btOps.end(), tops.begin() + (ptrdiff_t) topsOff[(size_t) j], tops.begin() + (ptrdiff_t) (topsOff[(size_t) j] + tres[(size_t) j].bt_len));
+            q->btOff.push_back(q->btOps.size());
+            q->btIds.push_back(path ? tres[(size_t) j].identities : 0u);
+        }
     }
     nAlnOut += o;
     return MK_OK;
@@ -1592,6 +1745,8 @@ int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if (!q->havePref) return fail(MK_ERR_ARG, "mk_align: the batch has no prefilter result");
     if ((rc = check_roles(db, q)) != MK_OK) return rc;
     if ((rc = check_filters(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
+    if ((rc = check_alignment_mode(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
+    q->btOps.clear(); q->btOff.clear(); q->btIds.clear(); q->haveBt = false; q->btLeftBand = 0;
     HostTimer htAll("host_align_total");
     std::shared_ptr<const ScoreTabs> tabs;
     {
@@ -1603,6 +1758,7 @@ int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     rc = align_range(db, q, P, 0, q->n, tabs->gate, &tabs->tables, g_stream, nAln);
     if (rc != MK_OK) return rc;
     q->haveAln = true;
+    if (P->add_backtrace == 1) { if (q->btOff.empty()) q->btOff.push_back(0); q->haveBt = true; }
     return MK_OK;
 }
 
@@ -1848,6 +2004,8 @@ int mk_search_begin(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if ((rc = check_indexed(db, "mk_search")) != MK_OK) return rc;
     if ((rc = check_roles(db, q)) != MK_OK) return rc;
     if ((rc = check_filters(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
+    if ((rc = check_alignment_mode(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
+    q->btOps.clear(); q->btOff.clear(); q->btIds.clear(); q->haveBt = false; q->btLeftBand = 0;
     SearchJob *job = new SearchJob();
     job->db = db; job->q = q; job->P = *P;
     job->hostThreads = omp_get_max_threads();
@@ -1876,6 +2034,7 @@ int mk_search_wait(mk_queries *q) {
     if (rc != MK_OK) g_err = job->err;
     else {
         q->havePref = true; q->haveAln = true;
+        if (job->P.add_backtrace == 1) { if (q->btOff.empty()) q->btOff.push_back(0); q->haveBt = true; }
         if (q->n > 0 && !q->isProfile) { g_hitsPerQuery.store((double) q->nHits / (double) q->n); g_alnsPerQuery.store((double) q->alnOff[q->n] / (double) q->n); }
     }
     q->job = nullptr;
@@ -1908,6 +2067,16 @@ int mk_align_result(const mk_queries *q, const mk_alignment **alns, const uint64
     return MK_OK;
 }
 
+int mk_align_backtrace(const mk_queries *q, const char **ops, const uint64_t **opsOffsets, const uint32_t **identities) {
+    if (!q || !q->haveAln || !q->haveBt) return fail(MK_ERR_ARG, "no backtraces available: the batch was not aligned with add_backtrace = 1");
+    if (ops) *ops = q->btOps.data();
+    if (opsOffsets) *opsOffsets = q->btOff.data();
+    if (identities) *identities = q->btIds.data();
+    return MK_OK;
+}
+// test hook (include/metaeuk_amd_debug.h): pairs of the batch's last alignment whose trace left the band
+uint64_t mk_debug_trace_left_band(const mk_queries *q) { return q ? q->btLeftBand : 0; }
+
 int mk_kernel_stats(mk_kernel_stat *out, int cap) {
     std::lock_guard<std::mutex> g(g_statsMutex);
     int k = 0;
@@ -1928,6 +2097,28 @@ size_t mk_format_alignment(char *buf, const mk_alignment *a) { return mk::format
 
 size_t mk_format_hits(char *buf, size_t cap, const mk_hit *hits, uint64_t n, const uint32_t *targetKeys) {
     return format_bulk(buf, cap, hits, n, 32, [&](char *w, const mk_hit &h) { return mk::format_hit(w, targetKeys ? targetKeys[h.seq_id] : h.seq_id, h.pref_score, h.diagonal); });
+}
+// Matcher::resultToBuffer with addBacktrace and compress (Matcher.cpp:312-317) over Matcher::compressAlignment (:166-185)
+size_t mk_format_alignment_bt(char *buf, const mk_alignment *a, const char *ops, uint64_t nOps) {
+    char *p = buf + mk::format_alignment(buf, *a);
+    p[-1] = '\t';
+    char state = 'M';
+    uint64_t counter = 0;
+    for (uint64_t i = 0; i < nOps; i++) {
+        if (ops[i] != state) { p += std::sprintf(p, "%llu", (unsigned long long) counter); *p++ = state; state = ops[i]; counter = 1; }
+        else counter++;
+    }
+    p += std::sprintf(p, "%llu", (unsigned long long) counter);
+    *p++ = state;
+    *p++ = '\n';
+    return (size_t) (p - buf);
+}
+size_t mk_format_alignments_bt(char *buf, size_t cap, const mk_alignment *alns, uint64_t n, const char *ops, const uint64_t *opsOffsets) {
+    if (!buf || (!alns && n) || !opsOffsets || (!ops && opsOffsets[n])) return 0;
+    if (cap < 176 * n + 3 * opsOffsets[n]) return 0;
+    size_t at = 0;
+    for (uint64_t k = 0; k < n; k++) at += mk_format_alignment_bt(buf + at, alns + k, ops + opsOffsets[k], opsOffsets[k + 1] - opsOffsets[k]);
+    return at;
 }
 size_t mk_format_alignments(char *buf, size_t cap, const mk_alignment *alns, uint64_t n) {
     return format_bulk(buf, cap, alns, n, 160, [&](char *w, const mk_alignment &a) { return mk::format_alignment(w, a); });

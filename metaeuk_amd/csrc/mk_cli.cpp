@@ -11,7 +11,7 @@
 // honoured, and a value that would change results in a way this build does not restate is a hard error
 // in EVERY command (the reference parser also fails hard on anything it does not know).  Omitted flags take
 // the module defaults of the reference (-e 0.001 for align / search, -s 4 for prefilter, 5.7 for search) with
-// one exception: `align` and `search` must be given --alignment-mode 2, because the module default (0 = auto)
+// one exception: `align` and `search` must be given --alignment-mode 2 or 3, because the module default (0 = auto)
 // resolves to score-only output, which is not built.  predictexons applies setPredictExonsDefaults.
 // Sharded commands (RANK / WORLD_SIZE or --shard r/N): every worker removes its own leftovers and stamps its
 // shard with the launch token before it computes, a failing worker leaves <out>_<r>.failed, worker 0 merges
@@ -61,8 +61,8 @@ const Flag FLAGS[] = {
     {"--add-self-matches", "0", false}, {"--spaced-kmer-mode", "1", false}, {"--spaced-kmer-pattern", "", false},
     {"--local-tmp", "", false}, {"--db-load-mode", "0", false}, {"--pca", "", false}, {"--pcb", "", false},
     {"--taxon-list", "", false}, {"--threads", "", true}, {"--compressed", "0", false}, {"-v", "3", true},
-    {"-a", "0", false}, {"--alignment-mode", "2", false}, {"--alignment-output-mode", "0", true}, {"--wrapped-scoring", "0", false},
-    {"-e", "100", true}, {"--min-seq-id", "0", true}, {"--min-aln-len", "0", true}, {"--seq-id-mode", "0", false},
+    {"-a", "0", true}, {"--alignment-mode", "2", true}, {"--alignment-output-mode", "0", true}, {"--wrapped-scoring", "0", false},
+    {"-e", "100", true}, {"--min-seq-id", "0", true}, {"--min-aln-len", "0", true}, {"--seq-id-mode", "0", true},
     {"--alt-ali", "0", false}, {"--max-rejected", "2147483647", false}, {"--max-accept", "2147483647", false},
     {"--score-bias", "0", false}, {"--realign", "0", false}, {"--realign-score-bias", "-0.2", false}, {"--realign-max-seqs", "2147483647", false},
     {"--corr-score-weight", "0", false}, {"--gap-open", "aa:11,nucl:5", true}, {"--gap-extend", "aa:1,nucl:2", true}, {"--zdrop", "40", false},
@@ -140,7 +140,7 @@ int parse(int argc, char **argv, Args &a) {
         if (std::string(k.name) == "--split-memory-limit" || std::string(k.name) == "--local-tmp" ||
             std::string(k.name) == "--db-load-mode" || std::string(k.name) == "--split" || std::string(k.name) == "--split-mode" ||
             std::string(k.name) == "--pca" || std::string(k.name) == "--pcb" || std::string(k.name) == "--zdrop" || std::string(k.name) == "--realign-score-bias" ||
-            std::string(k.name) == "--realign-max-seqs" || std::string(k.name) == "--seq-id-mode" || std::string(k.name) == "--mask-lower-case" ||
+            std::string(k.name) == "--realign-max-seqs" || std::string(k.name) == "--mask-lower-case" ||
             std::string(k.name) == "--threads" || std::string(k.name) == "--remove-tmp-files" || std::string(k.name) == "--reuse-latest" ||
             std::string(k.name) == "--force-reuse" || std::string(k.name) == "--disk-space-limit" || std::string(k.name) == "--mpi-runner") continue;    // no effect on this path
         if (std::string(k.name) == "--start-sens") continue;          // only read when --sens-steps > 1, which is refused below
@@ -189,6 +189,19 @@ int fillParams(const Args &a, mk_params &P, int &gpu) {
     if (!(P.cov_thr >= 0.0f && P.cov_thr <= 1.0f)) return die("-c %s: the coverage threshold is a fraction between 0 and 1", *get("-c"));
     if (auto v = get("--cov-mode")) if (v->size() != 1 || (*v)[0] < '0' || (*v)[0] > '5') return die("--cov-mode %s: coverage modes 0 to 5 exist", *v);
     if (!(P.seq_id_thr >= 0.0f && P.seq_id_thr <= 1.0f)) return die("--min-seq-id %s: the sequence identity threshold is a fraction between 0 and 1", *get("--min-seq-id"));
+    // --alignment-mode / -a / --seq-id-mode (Parameters.cpp; Alignment.cpp:35-37: -a turns the mode into 3): modes 2 and 3 are built
+    if (auto v = get("--alignment-mode")) {
+        if (*v != "2" && *v != "3") return die("--alignment-mode %s: only 2 (score, coverage, estimated identity) and 3 (exact identity from the backtrace) are implemented", *v);
+        P.alignment_mode = atoi(v->c_str());
+    }
+    if (auto v = get("-a")) {
+        if (*v != "0" && *v != "1") return die("-a %s: 0 or 1", *v);
+        P.add_backtrace = atoi(v->c_str());
+    }
+    if (auto v = get("--seq-id-mode")) {
+        if (*v != "0" && *v != "1" && *v != "2") return die("--seq-id-mode %s: 0 (alignment length), 1 (shorter sequence) and 2 (longer sequence) exist", *v);
+        P.seq_id_mode = atoi(v->c_str());
+    }
     if (auto v = get("--gap-open")) P.gap_open = atoi(aaPart(*v).c_str());
     if (auto v = get("--gap-extend")) P.gap_extend = atoi(aaPart(*v).c_str());
     if (auto v = get("--threads")) setenv("OMP_NUM_THREADS", v->c_str(), 0);
@@ -212,6 +225,10 @@ int refuseFiltersForProfiles(const mk_params &P) {
     if (P.cov_thr > 0.0f) return die("-c: only the default (0) is implemented with profile targets%s");
     if (P.cov_mode != 0) return die("--cov-mode: only the default (0) is implemented with profile targets%s");
     if (P.seq_id_thr > 0.0f) return die("--min-seq-id: only the default (0) is implemented with profile targets%s");
+    // ... and the backtrace of a profile (the PROFILE_SEQ branch of banded_sw, the I / D exchange of swapResult) is not restated either
+    if (P.alignment_mode == 3) return die("--alignment-mode 3: only mode 2 is implemented with profile targets%s");
+    if (P.add_backtrace != 0) return die("-a: only the default (0) is implemented with profile targets%s");
+    if (P.seq_id_mode != 0) return die("--seq-id-mode: only the default (0) is implemented with profile targets%s");
     return 0;
 }
 
@@ -595,7 +612,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     // the module's own default --alignment-mode 0 resolves to score-only output (Alignment.cpp:168-178), which is not built:
     // the caller has to ask for mode 2, as predictexons does (PredictExons.cpp:13)
     if (isAlign && a.opt.find("--alignment-mode") == a.opt.end())
-        return die("%s needs --alignment-mode 2 (the module default, 0 = score only, is not implemented)", isSearch ? "search" : "align");
+        return die("%s needs --alignment-mode 2 or 3 (the module default, 0 = score only, is not implemented)", isSearch ? "search" : "align");
     if (int rc = fillParams(a, P, gpu)) return rc;
     // --alignment-output-mode 1 (the per-slice `align` of the sliced profile workflow): the accepted targets' keys only
     const bool keyListOut = isAlign && a.opt.count("--alignment-output-mode") && a.opt["--alignment-output-mode"] == "1";
@@ -785,6 +802,10 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         }
         const mk_alignment *alns; const uint64_t *aoff;
         mk_align_result(Q, &alns, &aoff);
+        // -a: the 11th column, Matcher::compressAlignment of the backtrace (Matcher.cpp:312-317)
+        const char *btOps = nullptr; const uint64_t *btOff = nullptr;
+        if (P.add_backtrace && mk_align_backtrace(Q, &btOps, &btOff, nullptr) != MK_OK) return die("%s", mk_last_error());
+        std::vector<char> wide;
         mk::DatabaseWriter w(outPath, keyListOut ? 6 /* DBTYPE_CLUSTER_RES, Alignment.cpp:250-252 */ : mk::DBTYPE_ALIGNMENT_RES);
         e = w.open();
         if (!e.empty()) return die("%s", e);
@@ -794,6 +815,12 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
                 mk_alignment al = alns[k];
                 al.db_key = tkeys[al.db_key];
                 if (keyListOut) { buf.append(line, (size_t) snprintf(line, sizeof(line), "%u\n", al.db_key)); continue; }   // Alignment.cpp:499-503
+                if (P.add_backtrace) {
+                    const uint64_t nOps = btOff[k + 1] - btOff[k];
+                    wide.resize(192 + 12 * (size_t) nOps);
+                    buf.append(wide.data(), mk_format_alignment_bt(wide.data(), &al, btOps + btOff[k], nOps));
+                    continue;
+                }
                 buf.append(line, mk_format_alignment(line, &al));
             }
             w.write(qdb.entries[i].key, buf.data(), buf.size());
@@ -843,6 +870,11 @@ int cmdSwapResults(int argc, char **argv) {
             unsigned key = 0; char sid[64], ev[64];
             if (sscanf(p, "%u\t%d\t%63s\t%63s\t%d\t%d\t%d\t%d\t%d\t%d", &key, &x.bit_score, sid, ev, &x.q_start, &x.q_end, &x.q_len, &x.db_start, &x.db_end, &x.db_len) != 10)
                 return die("Invalid alignment result record in %s", a.pos[2]);
+            {   // an 11th column is the backtrace of `align -a`: swapping it (Matcher::result_t::swapResult exchanges I and D) is not implemented
+                int tabs = 0;
+                for (const char *c = p; *c != '\n' && *c != '\0'; c++) tabs += *c == '\t';
+                if (tabs >= 10) return die("swapresults: %s holds alignment records with a backtrace column (-a), which is not implemented", a.pos[2]);
+            }
             auto ti = tKeyToIdx.find(key);
             if (ti == tKeyToIdx.end()) return die("swapresults: key %s of the result DB is not in the target DB", std::to_string(key));
             x.db_key = ti->second;
@@ -1202,6 +1234,9 @@ int cmdPredictExons(int argc, char **argv) {
     if (auto v = get("--set-gap-open")) X.gap_open = atoi(v->c_str());
     if (auto v = get("--set-gap-extend")) X.gap_extend = atoi(v->c_str());
     if (!get("-e")) P.evalue_thr = 100;                          // setPredictExonsDefaults (PredictExons.cpp:8-16)
+    // -a 1: the search runs in mode 3 (Alignment.cpp:35-37) and the exon stages read the exact identities; the backtrace itself reaches none of
+    // predictexons' outputs (resultspercontig.cpp:177 parses it away), so the strings are not kept
+    if (P.add_backtrace) { P.alignment_mode = 3; P.add_backtrace = 0; }
     if (!get("--min-aln-len")) P.min_aln_len = (int) X.min_exon_aa;   // par.alnLenThr = par.minExonAaLength (:46)
     if (mk::Database::exists(a.pos[2] + ".dbtype")) return die("%s exists already!", a.pos[2]);          // predictexons.sh:32
     const double t0 = now();
