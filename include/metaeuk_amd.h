@@ -254,17 +254,36 @@ int mk_align_result(const mk_queries *q, const mk_alignment **alns, const uint64
  * Views owned by the batch handle.  MK_ERR_ARG when the batch was not aligned with add_backtrace. */
 int mk_align_backtrace(const mk_queries *q, const char **ops, const uint64_t **ops_offsets /* n_alignments + 1 */, const uint32_t **identities);
 
-/* ---- producer of the query batch: `extractorfs --translate` as predictexons runs it
- * (util/extractorfs.cpp:19-159, Orf::findAll with orf-start-mode 1, all six frames, genetic code 1, contig start / end mode
- * 2).  Contigs are ASCII nucleotides (IUPAC codes, lower case, U allowed), concatenated, offsets[n_contigs + 1].
- * Fragment k is what the reference's renumbered ORF DB holds under key k. */
+/* ---- producer of the query batch: `extractorfs` + `translatenucs` (+ `reverseseq`) as predictexons runs
+ * them (util/extractorfs.cpp:19-159, Orf::findAll with orf-start-mode 1, contig start mode 2, genetic code 1; the frames, the gap and
+ * length limits, the contig end mode and the null mode are mk_orf_params).  Contigs are ASCII nucleotides (IUPAC codes, lower case,
+ * U allowed), concatenated, offsets[n_contigs + 1].  Fragment k is what the reference's renumbered ORF DB holds under key k: the order
+ * is contig, plus strand then minus strand, end position ascending, whatever the parameters drop. */
 typedef struct mk_orfs mk_orfs;
 typedef struct mk_orf {
     uint32_t contig;            /* index of the contig */
     uint32_t from, to;          /* Orf::writeOrfHeader coordinates on the contig (from > to on the minus strand) */
     uint8_t incomplete_start, incomplete_end, minus_strand, pad_;
 } mk_orf;
+typedef struct {               /* the extractorfs flags (Parameters.cpp:2525-2554) + --reverse-fragments (predictexons.sh:53-62) */
+    int min_codons;            /* --min-length       15; >= 1 */
+    int max_codons;            /* --max-length       32734; 1 .. 65535 (a fragment's length is kept in 16 bits, and translatenucs cuts there):
+                                                     0 or negative MK_ERR_ARG, above 65535 MK_ERR_UNSUPPORTED */
+    int max_gap_codons;        /* --max-gaps         2147483647 = no limit; a fragment with more codons that hold an N or a non-IUPAC
+                                                     character is dropped (it still closes its frame); negative MK_ERR_ARG */
+    int forward_frames;        /* --forward-frames   bit f - 1 = frame f of the plus strand (7 = "1,2,3"), 0 skips the strand; above 7 MK_ERR_ARG */
+    int reverse_frames;        /* --reverse-frames   the same on the reverse complement: frame f starts at ITS position f - 1 */
+    int contig_end_mode;       /* --contig-end-mode  0: only fragments without a closing stop, 1: only those with one, 2: both; else MK_ERR_ARG */
+    int reverse_fragments;     /* --reverse-fragments 0 / 1 (else MK_ERR_ARG): every protein back to front, records and headers unchanged */
+    int pad_;
+} mk_orf_params;
+void mk_default_orf_params(mk_orf_params *p);
+int mk_extract_orfs_ex(const char *nucleotides, const uint64_t *offsets, uint32_t n_contigs, const mk_orf_params *params, mk_orfs **out);
+/* = mk_extract_orfs_ex with the defaults and this min_codons */
 int mk_extract_orfs(const char *nucleotides, const uint64_t *offsets, uint32_t n_contigs, int min_codons, mk_orfs **out);
+/* the same fragments computed on the host, over the same restatement of the rule as the kernels (csrc/mk_orf_scan.hpp): no GPU call, no
+ * mk_init needed.  The handle works with every mk_orfs_* call; mk_queries_from_orfs uploads its residue codes. */
+int mk_extract_orfs_host(const char *nucleotides, const uint64_t *offsets, uint32_t n_contigs, const mk_orf_params *params, mk_orfs **out);
 /* fragments, their translations (ASCII, case preserved) as aa[aa_offsets[k] .. aa_offsets[k+1]) ; views owned by the handle */
 int mk_orfs_result(const mk_orfs *o, const mk_orf **orfs, const uint64_t **aa_offsets, const char **aa, uint64_t *n_orfs);
 /* the fragments as a query batch: the residue codes go from the translation kernel to the search without leaving HBM */

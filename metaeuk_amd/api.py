@@ -52,7 +52,8 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_targetdb_masked_residues", "mk_targetdb_kmer_size", "mk_targetdb_longest_list", "mk_targetdb_index_compare",
            "mk_synth_targets", "mk_synth_fragments", "mk_synth_seqdb", "mk_synth_write_seqdb", "mk_targetdb_create_sequences", "mk_prefilter_statistics",
            "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size",
-           "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band"]
+           "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band",
+           "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host"]
 
 
 def lib():
@@ -394,16 +395,41 @@ ORF_DTYPE = np.dtype([("contig", "<u4"), ("from", "<u4"), ("to", "<u4"), ("incom
                       ("minus_strand", "u1"), ("pad_", "u1")])
 
 
-class Orfs:
-    """six-frame ORF fragments of a list of contigs (nucleotide strings), translated on the GPU"""
+class OrfParams(C.Structure):
+    """mk_orf_params: the extractorfs flags + --reverse-fragments (include/metaeuk_amd.h)"""
+    _fields_ = [("min_codons", C.c_int), ("max_codons", C.c_int), ("max_gap_codons", C.c_int), ("forward_frames", C.c_int),
+                ("reverse_frames", C.c_int), ("contig_end_mode", C.c_int), ("reverse_fragments", C.c_int), ("pad_", C.c_int)]
 
-    def __init__(self, contigs, min_codons=15):
+
+def default_orf_params(**kw):
+    p = OrfParams()
+    lib().mk_default_orf_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(OrfParams._fields_):
+            raise TypeError("mk_orf_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def frame_mask(frames):
+    """Orf::getFrames: "1,3" -> 5; elements other than 1, 2, 3 are ignored ("0" -> no frame)"""
+    return sum(1 << (f - 1) for f in (1, 2, 3) if str(f) in str(frames).split(","))
+
+
+class Orfs:
+    """ORF fragments of a list of contigs (nucleotide strings), translated on the GPU; params = OrfParams (None: the defaults with
+    min_codons), host = True: the same fragments from the host twin, without a GPU call"""
+
+    def __init__(self, contigs, min_codons=15, params=None, host=False):
         raw = "".join(contigs).encode("latin-1")
         off = np.zeros(len(contigs) + 1, dtype=np.uint64)
         np.cumsum([len(c) for c in contigs], out=off[1:])
         self.h = C.c_void_p()
         self.n_contigs = len(contigs)
-        _chk(lib().mk_extract_orfs(C.c_char_p(raw), _p(off), C.c_uint32(len(contigs)), C.c_int(min_codons), C.byref(self.h)))
+        if params is None:
+            params = default_orf_params(min_codons=min_codons)
+        fn = lib().mk_extract_orfs_host if host else lib().mk_extract_orfs_ex
+        _chk(fn(C.c_char_p(raw), _p(off), C.c_uint32(len(contigs)), C.byref(params), C.byref(self.h)))
         op, fp, ap, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
         _chk(lib().mk_orfs_result(self.h, C.byref(op), C.byref(fp), C.byref(ap), C.byref(n)))
         self.n = int(n.value)

@@ -1164,16 +1164,58 @@ struct mk_orfs {
     ~mk_orfs() { dev.release(); }
 };
 
-int mk_extract_orfs(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, int minCodons, mk_orfs **out) {
-    // (round 6) like mk_queries_create this does NOT wait for the searches in flight: the contigs of the next batch are uploaded, scanned and translated
-    // on the upload stream with scratch buffers and pooled device blocks of their own, beside the search of the previous batch
-    int rc = ensure_ready(false);
-    if (rc) return rc;
-    if (!offsets || !out || (!nucleotides && offsets[nContigs] > 0) || minCodons < 1) return fail(MK_ERR_ARG, "bad argument");
+void mk_default_orf_params(mk_orf_params *p) {
+    if (!p) return;
+    p->min_codons = 15; p->max_codons = 32734; p->max_gap_codons = INT_MAX;        // Parameters.cpp: orfMinLength, orfMaxLength, orfMaxGaps
+    p->forward_frames = 7; p->reverse_frames = 7; p->contig_end_mode = 2; p->reverse_fragments = 0; p->pad_ = 0;
+}
+
+// the checks the device call and the host twin share: arguments, then the rule of mk_orf_scan.hpp
+static int orf_rule_of(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, const mk_orf_params *P, mk_orfs **out, mk::OrfRule &rule) {
+    if (!offsets || !out || !P || (!nucleotides && offsets[nContigs] > 0)) return fail(MK_ERR_ARG, "bad argument");
+    if (P->min_codons < 1) return fail(MK_ERR_ARG, "min_codons %d: at least 1", P->min_codons);
+    if (P->max_codons < 1) return fail(MK_ERR_ARG, "max_codons %d: at least 1", P->max_codons);
+    if (P->max_gap_codons < 0) return fail(MK_ERR_ARG, "max_gap_codons %d: not negative", P->max_gap_codons);
+    if (P->forward_frames < 0 || P->forward_frames > 7 || P->reverse_frames < 0 || P->reverse_frames > 7)
+        return fail(MK_ERR_ARG, "frame masks %d / %d: three bits, frame f = bit f - 1", P->forward_frames, P->reverse_frames);
+    if (P->contig_end_mode < 0 || P->contig_end_mode > 2) return fail(MK_ERR_ARG, "contig_end_mode %d: 0, 1 or 2", P->contig_end_mode);
+    if (P->reverse_fragments != 0 && P->reverse_fragments != 1) return fail(MK_ERR_ARG, "reverse_fragments %d: 0 or 1", P->reverse_fragments);
+    if (P->max_codons > 65535) return fail(MK_ERR_UNSUPPORTED, "max_codons %d: at most 65535 codons per fragment (--max-length)", P->max_codons);
     for (uint32_t i = 0; i < nContigs; i++) {
         if (offsets[i + 1] < offsets[i]) return fail(MK_ERR_ARG, "offsets are not ascending at contig %u", i);
         if (offsets[i + 1] - offsets[i] >= 0x7FFFFFF0ull) return fail(MK_ERR_UNSUPPORTED, "contig %u is >= 2^31 nucleotides", i);
     }
+    rule.min_length = (uint32_t) P->min_codons; rule.max_length = (uint32_t) P->max_codons; rule.max_gaps = (uint32_t) P->max_gap_codons;
+    rule.forward_frames = (uint32_t) P->forward_frames; rule.reverse_frames = (uint32_t) P->reverse_frames;
+    rule.end_mode = (uint32_t) P->contig_end_mode; rule.reverse = (uint32_t) P->reverse_fragments;
+    return MK_OK;
+}
+
+// fragment records in strand coordinates -> Orf::writeOrfHeader coordinates on the contig
+static void orf_headers(const std::vector<mk::OrfRecord> &rec, const uint64_t *offsets, std::vector<mk_orf> &orfs) {
+    const uint64_t nf = rec.size();
+    orfs.resize(nf);
+#pragma omp parallel for schedule(static)
+    for (uint64_t k = 0; k < nf; k++) {
+        const mk::OrfRecord &r = rec[k];
+        const uint32_t len = (uint32_t) (offsets[r.contig + 1] - offsets[r.contig]);
+        const uint32_t sTo = r.s_from + 3 * r.n_aa - 1;           // strand coordinates; the minus strand is mirrored (extractorfs.cpp:88-93)
+        mk_orf &h = orfs[k];
+        h.contig = r.contig;
+        h.minus_strand = (r.flags & 4u) ? 1 : 0;
+        h.from = h.minus_strand ? (len - 1) - r.s_from : r.s_from;
+        h.to = h.minus_strand ? (len - 1) - sTo : sTo;
+        h.incomplete_start = (r.flags & 1u) ? 1 : 0; h.incomplete_end = (r.flags & 2u) ? 1 : 0; h.pad_ = 0;
+    }
+}
+
+int mk_extract_orfs_ex(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, const mk_orf_params *P, mk_orfs **out) {
+    // (round 6) like mk_queries_create this does NOT wait for the searches in flight: the contigs of the next batch are uploaded, scanned and translated
+    // on the upload stream with scratch buffers and pooled device blocks of their own, beside the search of the previous batch
+    int rc = ensure_ready(false);
+    if (rc) return rc;
+    mk::OrfRule rule;
+    if ((rc = orf_rule_of(nucleotides, offsets, nContigs, P, out, rule)) != MK_OK) return rc;
     HostTimer ht("host_extract_orfs_total");
     hipStream_t up = g_uploadStream ? g_uploadStream : g_stream;
     struct Restore {
@@ -1193,7 +1235,7 @@ int mk_extract_orfs(const char *nucleotides, const uint64_t *offsets, uint32_t n
     if (e != hipSuccess) { delete o; return fail(MK_ERR_DEVICE, "contig upload failed: %s", hipGetErrorString(e)); }
     std::string err;
     const int th = timed_begin("extract_orfs", (double) offsets[nContigs] * 2.0, 0);
-    rc = mk::run_extract_orfs(dNucl.p, dOff.p, nContigs, (uint32_t) minCodons, 32734u, (uint64_t) INT_MAX, up, o->dev, err);
+    rc = mk::run_extract_orfs(dNucl.p, dOff.p, nContigs, rule, up, o->dev, err);
     timed_end(th);
     timed_flush();
     if (rc != MK_OK) { delete o; return fail(rc, "%s", err.c_str()); }
@@ -1207,19 +1249,28 @@ int mk_extract_orfs(const char *nucleotides, const uint64_t *offsets, uint32_t n
         if (c == hipSuccess) c = hipMemcpyAsync(o->codes.data(), o->dev.aa_code, na, hipMemcpyDeviceToHost, up);
         if (c == hipSuccess) c = hipStreamSynchronize(up);
         if (c != hipSuccess) { delete o; return fail(MK_ERR_DEVICE, "fragment download failed: %s", hipGetErrorString(c)); }
-#pragma omp parallel for schedule(static)
-        for (uint64_t k = 0; k < nf; k++) {
-            const mk::OrfRecord &r = rec[k];
-            const uint32_t len = (uint32_t) (offsets[r.contig + 1] - offsets[r.contig]);
-            const uint32_t sTo = r.s_from + 3 * r.n_aa - 1;           // strand coordinates; the minus strand is mirrored (extractorfs.cpp:88-93)
-            mk_orf &h = o->orfs[k];
-            h.contig = r.contig;
-            h.minus_strand = (r.flags & 4u) ? 1 : 0;
-            h.from = h.minus_strand ? (len - 1) - r.s_from : r.s_from;
-            h.to = h.minus_strand ? (len - 1) - sTo : sTo;
-            h.incomplete_start = (r.flags & 1u) ? 1 : 0; h.incomplete_end = (r.flags & 2u) ? 1 : 0; h.pad_ = 0;
-        }
+        orf_headers(rec, offsets, o->orfs);
     }
+    *out = o;
+    return MK_OK;
+}
+
+int mk_extract_orfs(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, int minCodons, mk_orfs **out) {
+    mk_orf_params P;
+    mk_default_orf_params(&P);
+    P.min_codons = minCodons;
+    return mk_extract_orfs_ex(nucleotides, offsets, nContigs, &P, out);
+}
+
+int mk_extract_orfs_host(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, const mk_orf_params *P, mk_orfs **out) {
+    mk::OrfRule rule;
+    if (int rc = orf_rule_of(nucleotides, offsets, nContigs, P, out, rule)) return rc;
+    mk::OrfHostResult H;
+    mk::extract_orfs_host(nucleotides, offsets, nContigs, rule, H);
+    mk_orfs *o = new mk_orfs();
+    o->nContigs = nContigs;
+    orf_headers(H.records, offsets, o->orfs);
+    o->aaOff.swap(H.aa_off); o->aa.swap(H.aa); o->codes.swap(H.codes);
     *out = o;
     return MK_OK;
 }

@@ -67,13 +67,13 @@ const Flag FLAGS[] = {
     {"--score-bias", "0", false}, {"--realign", "0", false}, {"--realign-score-bias", "-0.2", false}, {"--realign-max-seqs", "2147483647", false},
     {"--corr-score-weight", "0", false}, {"--gap-open", "aa:11,nucl:5", true}, {"--gap-extend", "aa:1,nucl:2", true}, {"--zdrop", "40", false},
     // predictexons only: extractorfs (Parameters.cpp:2525-2554), search workflow extras, collectoptimalset (LocalParameters.h:92-104)
-    {"--min-length", "15", true}, {"--max-length", "32734", false}, {"--max-gaps", "2147483647", false}, {"--contig-start-mode", "2", false},
-    {"--contig-end-mode", "2", false}, {"--orf-start-mode", "1", false}, {"--forward-frames", "1,2,3", false}, {"--reverse-frames", "1,2,3", false},
-    {"--translation-table", "1", false}, {"--translate", "0", false}, {"--use-all-table-starts", "0", false}, {"--id-offset", "0", false},
+    {"--min-length", "15", true}, {"--max-length", "32734", true}, {"--max-gaps", "2147483647", true}, {"--contig-start-mode", "2", false},
+    {"--contig-end-mode", "2", true}, {"--orf-start-mode", "1", false}, {"--forward-frames", "1,2,3", true}, {"--reverse-frames", "1,2,3", true},
+    {"--translation-table", "1", false}, {"--translate", "0", false}, {"--use-all-table-starts", "0", true}, {"--id-offset", "0", false},
     {"--create-lookup", "0", false}, {"--add-orf-stop", "0", false}, {"--num-iterations", "1", false}, {"--start-sens", "4", false},
     {"--sens-steps", "1", false}, {"--exhaustive-search", "0", false}, {"--exhaustive-search-filter", "0", false}, {"--strand", "1", false},
     {"--remove-tmp-files", "0", false}, {"--reuse-latest", "0", false}, {"--force-reuse", "0", false}, {"--disk-space-limit", "0", false},
-    {"--mpi-runner", "", false}, {"--reverse-fragments", "0", false},
+    {"--mpi-runner", "", false}, {"--reverse-fragments", "0", true},
     {"--metaeuk-eval", "0.001", true}, {"--metaeuk-tcov", "0.5", true}, {"--max-intron", "10000", true}, {"--min-intron", "15", true},
     {"--min-exon-aa", "11", true}, {"--max-overlap", "10", true}, {"--max-exon-sets", "1", true}, {"--set-gap-open", "-1", true},
     {"--set-gap-extend", "-1", true},
@@ -229,6 +229,54 @@ int refuseFiltersForProfiles(const mk_params &P) {
     if (P.alignment_mode == 3) return die("--alignment-mode 3: only mode 2 is implemented with profile targets%s");
     if (P.add_backtrace != 0) return die("-a: only the default (0) is implemented with profile targets%s");
     if (P.seq_id_mode != 0) return die("--seq-id-mode: only the default (0) is implemented with profile targets%s");
+    return 0;
+}
+
+// the extractorfs flags (Parameters.cpp:2525-2554) and --reverse-fragments of a command line -> mk_orf_params, for `extractorfs` and
+// `predictexons` alike.  Honoured: --min-length, --max-length, --max-gaps, --forward-frames, --reverse-frames, --contig-end-mode,
+// --reverse-fragments; --use-all-table-starts is read and has no effect with orf-start-mode 1 (Orf.cpp:284-290: only START_TO_STOP and
+// LAST_START_TO_STOP look at start codons).  Refused by name: another --orf-start-mode, --contig-start-mode (the reference itself exits
+// with orf-start-mode 1 below 2, extractorfs.cpp:38-41), --translation-table, --add-orf-stop.
+int fillOrfParams(const Args &a, mk_orf_params &O) {
+    mk_default_orf_params(&O);
+    auto get = [&](const char *k) -> const std::string * { auto it = a.opt.find(k); return it == a.opt.end() ? nullptr : &it->second; };
+    static const char *const fixed[][2] = {{"--orf-start-mode", "1"}, {"--contig-start-mode", "2"}, {"--translation-table", "1"}, {"--add-orf-stop", "0"}};
+    for (const auto &f : fixed)
+        if (auto v = get(f[0])) if (!sameValue(*v, f[1])) {
+            fprintf(stderr, "%s %s: only the default (%s) is implemented by the MI355X path\n", f[0], v->c_str(), f[1]);
+            return EXIT_FAILURE;
+        }
+    auto number = [&](const char *k, int &dst) -> int {                  // non-negative integers, like the reference's ^[0-9]+$ patterns
+        auto v = get(k);
+        if (!v) return 0;
+        char *end;
+        const long long x = strtoll(v->c_str(), &end, 10);
+        if (end == v->c_str() || *end != 0 || x < 0) { fprintf(stderr, "%s %s: a non-negative integer is expected\n", k, v->c_str()); return EXIT_FAILURE; }
+        dst = (int) std::min<long long>(x, std::numeric_limits<int>::max());
+        return 0;
+    };
+    auto frames = [](const std::string &v) {                             // Orf::getFrames: membership of "1", "2", "3" in the comma list
+        int mask = 0;
+        for (size_t p = 0; p <= v.size(); ) {
+            const size_t c = std::min(v.find(',', p), v.size());
+            const std::string e = v.substr(p, c - p);
+            if (e == "1") mask |= 1; else if (e == "2") mask |= 2; else if (e == "3") mask |= 4;
+            p = c + 1;
+        }
+        return mask;
+    };
+    int startsAll = 0;
+    if (number("--min-length", O.min_codons) || number("--max-length", O.max_codons) || number("--max-gaps", O.max_gap_codons) ||
+        number("--contig-end-mode", O.contig_end_mode) || number("--reverse-fragments", O.reverse_fragments) || number("--use-all-table-starts", startsAll))
+        return EXIT_FAILURE;
+    if (auto v = get("--forward-frames")) O.forward_frames = frames(*v);
+    if (auto v = get("--reverse-frames")) O.reverse_frames = frames(*v);
+    if (O.contig_end_mode > 2) return die("--contig-end-mode %s: 0, 1 or 2", *get("--contig-end-mode"));
+    if (O.reverse_fragments > 1) return die("--reverse-fragments %s: 0 or 1", *get("--reverse-fragments"));
+    if (startsAll > 1) return die("--use-all-table-starts %s: 0 or 1", *get("--use-all-table-starts"));
+    if (O.max_codons > 65535) return die("--max-length %s: at most 65535 codons per fragment are implemented", *get("--max-length"));
+    if (O.min_codons < 1) return die("--min-length %s: at least 1", *get("--min-length"));
+    if (O.max_codons < 1) return die("--max-length %s: at least 1", *get("--max-length"));
     return 0;
 }
 
@@ -918,35 +966,37 @@ size_t contigBatchEnd(const mk::Database &contigs, const std::vector<size_t> &or
     return c1;
 }
 
-// extractorfs <i:contigDB> <o:orfDB> [--min-length 15] [--translate 0|1] [--aa-sibling NAME] [--gpu N]
-//   = util/extractorfs.cpp for predictexons' settings: nucleotide (or, --translate 1, amino-acid) ORF fragments under
+// extractorfs <i:contigDB> <o:orfDB> [--min-length 15] [--max-length 32734] [--max-gaps 2147483647] [--forward-frames 1,2,3]
+//             [--reverse-frames 1,2,3] [--contig-end-mode 2] [--translate 0|1] [--aa-sibling NAME] [--gpu N]
+//   = util/extractorfs.cpp with orf-start-mode 1: nucleotide (or, --translate 1, amino-acid) ORF fragments under
 //   renumbered keys 0..N-1 plus the header DB <o>_h ("contigKey<TAB>from(+|-)len[<TAB>complete]").  --aa-sibling NAME also
 //   writes the translated fragments as the DB NAME next to <o>: predictexons.sh:47 skips `translatenucs` when aa_6f exists.
 int cmdExtractOrfs(int argc, char **argv) {
-    std::vector<std::string> pos;
-    int minLength = 15, translate = 0, gpu = 0;
+    Args args;
+    int translate = 0, gpu = 0;
     std::string sibling;
     if (const char *lr = launcherEnv("LOCAL_RANK")) gpu = atoi(lr);
+    // the command's own parameter list (Parameters.cpp:2525-2554) + --aa-sibling / --gpu; the ORF flags are read by fillOrfParams, like predictexons'
+    static const char *const known[] = {"--min-length", "--max-length", "--max-gaps", "--contig-start-mode", "--contig-end-mode", "--orf-start-mode",
+                                        "--forward-frames", "--reverse-frames", "--translation-table", "--translate", "--use-all-table-starts",
+                                        "--id-offset", "--create-lookup", "--add-orf-stop", "--threads", "--compressed", "-v", "--gpu", "--aa-sibling"};
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
-        auto val = [&](int &dst) { if (i + 1 >= argc) return false; dst = atoi(argv[++i]); return true; };
-        if (a == "--min-length") { if (!val(minLength)) return die("missing value for %s", a); }
-        else if (a == "--translate") { if (!val(translate)) return die("missing value for %s", a); }
-        else if (a == "--gpu") { if (!val(gpu)) return die("missing value for %s", a); }
-        else if (a == "--aa-sibling") { if (i + 1 >= argc) return die("missing value for %s", a); sibling = argv[++i]; }
-        else if (a == "--orf-start-mode" || a == "--contig-start-mode" || a == "--contig-end-mode" || a == "--max-length" || a == "--max-gaps" ||
-                 a == "--forward-frames" || a == "--reverse-frames" || a == "--translation-table" || a == "--use-all-table-starts" ||
-                 a == "--threads" || a == "--compressed" || a == "-v" || a == "--id-offset" || a == "--create-lookup") {
-            // accepted when they carry predictexons' values (Parameters.cpp:2525-2554, PredictExons.cpp:9-11); anything else is an error
-            if (i + 1 >= argc) return die("missing value for %s", a);
-            const std::string v = argv[++i];
-            const char *want = a == "--orf-start-mode" ? "1" : a == "--contig-start-mode" ? "2" : a == "--contig-end-mode" ? "2" : a == "--max-length" ? "32734"
-                             : a == "--max-gaps" ? "2147483647" : a == "--forward-frames" ? "1,2,3" : a == "--reverse-frames" ? "1,2,3" : a == "--translation-table" ? "1"
-                             : a == "--use-all-table-starts" ? "0" : a == "--compressed" ? "0" : a == "--id-offset" ? "0" : a == "--create-lookup" ? "0" : nullptr;
-            if (want && v != want) return die(("this build implements " + a + " " + want + " only, got %s").c_str(), v);
-        } else if (!a.empty() && a[0] == '-') return die("Unrecognized parameter %s", a);
-        else pos.push_back(a);
+        if (a.empty() || a[0] != '-') { args.pos.push_back(a); continue; }
+        bool ok = false;
+        for (const char *k : known) ok = ok || a == k;
+        if (!ok) return die("Unrecognized parameter %s", a);
+        if (i + 1 >= argc) return die("missing value for %s", a);
+        args.opt[a] = argv[++i];
     }
+    const std::vector<std::string> &pos = args.pos;
+    mk_orf_params orfP;
+    if (int rc = fillOrfParams(args, orfP)) return rc;
+    for (const char *k : {"--compressed", "--id-offset", "--create-lookup"})      // written uncompressed, keys from 0, no lookup file
+        if (args.opt.count(k) && args.opt[k] != "0") return die(("this build implements " + std::string(k) + " 0 only, got %s").c_str(), args.opt[k]);
+    if (args.opt.count("--translate")) translate = atoi(args.opt["--translate"].c_str());
+    if (args.opt.count("--gpu")) gpu = atoi(args.opt["--gpu"].c_str());
+    if (args.opt.count("--aa-sibling")) sibling = args.opt["--aa-sibling"];
     if (pos.size() != 2) return die("usage: metaeuk-amd extractorfs <i:sequenceDB> <o:sequenceDB> [--min-length N] [--translate 0|1]%s", "");
     if (mk_init(gpu) != MK_OK) return die("%s", mk_last_error());
     mk::Database contigs;
@@ -985,7 +1035,7 @@ int cmdExtractOrfs(int argc, char **argv) {
         }
         mk_orfs *O = nullptr;
         static const char none = 0;
-        if (mk_extract_orfs(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), minLength, &O) != MK_OK) return die("%s", mk_last_error());
+        if (mk_extract_orfs_ex(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), &orfP, &O) != MK_OK) return die("%s", mk_last_error());
         const mk_orf *orfs; const uint64_t *aaOff; const char *aa; uint64_t nb = 0;
         mk_orfs_result(O, &orfs, &aaOff, &aa, &nb);
         for (uint64_t k = 0; k < nb; k++) {
@@ -1123,7 +1173,7 @@ int invertedProfileSearch(const mk::Database &pdb, mk_targetdb *F, uint64_t nFra
 // lists again, to "keep the top hits") accepts exactly the pairs of the first with --max-accept / --max-rejected at their defaults, so one
 // pass is the result.  Sharded launches split the PROFILES: every worker translates all contigs and indexes all fragments (their number
 // enters the e-value threshold, the e-values and --max-seqs), worker 0 gathers the alignments, swaps and predicts (invertedProfileSearch).
-int predictExonsProfileTargets(const Args &a, mk_params P, const mk_exon_params &X, int minLength, const mk::Database &contigs, const std::vector<size_t> &ord,
+int predictExonsProfileTargets(const Args &a, mk_params P, const mk_exon_params &X, const mk_orf_params &orfP, const mk::Database &contigs, const std::vector<size_t> &ord,
                                const Shard &sh, const std::string &outPath, double t0) {
     static const char none = 0;
     mk::Database pdb;
@@ -1144,7 +1194,7 @@ int predictExonsProfileTargets(const Args &a, mk_params P, const mk_exon_params 
                 off.push_back(nucl.size());
             }
             mk_orfs *O = nullptr;
-            if (mk_extract_orfs(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), minLength, &O) != MK_OK) return die("%s", mk_last_error());
+            if (mk_extract_orfs_ex(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), &orfP, &O) != MK_OK) return die("%s", mk_last_error());
             const mk_orf *ob; const uint64_t *ao; const char *aab; uint64_t nb = 0;
             mk_orfs_result(O, &ob, &ao, &aab, &nb);
             const uint64_t base = aaOffAll.back();
@@ -1222,8 +1272,8 @@ int cmdPredictExons(int argc, char **argv) {
     auto get = [&](const char *k) -> const std::string * { auto it = a.opt.find(k); return it == a.opt.end() ? nullptr : &it->second; };
     mk_exon_params X;
     mk_default_exon_params(&X);
-    int minLength = 15;
-    if (auto v = get("--min-length")) minLength = atoi(v->c_str());
+    mk_orf_params orfP;                                          // one parsed set for every mk_extract_orfs_ex call of the command
+    if (int rc = fillOrfParams(a, orfP)) return rc;
     if (auto v = get("--metaeuk-eval")) X.evalue_thr = (double) (float) atof(v->c_str());      // float parameters (LocalParameters.h:76-77)
     if (auto v = get("--metaeuk-tcov")) X.target_cov_thr = (double) (float) atof(v->c_str());
     if (auto v = get("--max-intron")) X.max_intron = strtoull(v->c_str(), nullptr, 10);
@@ -1257,7 +1307,8 @@ int cmdPredictExons(int argc, char **argv) {
         if (f) { if (fread(&t, 4, 1, f) != 1) t = -1; fclose(f); }
         if (t >= 0 && (t & 0xFFFF) == DBTYPE_HMM_PROFILE) {
             if (int rc = refuseFiltersForProfiles(P)) return rc;
-            return predictExonsProfileTargets(a, P, X, minLength, contigs, ord, sh, a.pos[2], t0);
+            if (orfP.reverse_fragments) return die("--reverse-fragments 1: only the default (0) is implemented with profile targets%s");
+            return predictExonsProfileTargets(a, P, X, orfP, contigs, ord, sh, a.pos[2], t0);
         }
         if (get("--exhaustive-search") && *get("--exhaustive-search") != "0") return die("--exhaustive-search 1 with a sequence target database is not implemented%s");
     }
@@ -1308,7 +1359,7 @@ int cmdPredictExons(int argc, char **argv) {
                     nuclP.insert(nuclP.end(), contigs.entry(ord[i]), contigs.entry(ord[i]) + contigs.seqLen(ord[i]));
                     offP.push_back(nuclP.size());
                 }
-                if (mk_extract_orfs(nuclP.empty() ? &none : nuclP.data(), offP.data(), (uint32_t) pre.c1, minLength, &pre.O) != MK_OK) { pre.rc = EXIT_FAILURE; pre.err = mk_last_error(); return; }
+                if (mk_extract_orfs_ex(nuclP.empty() ? &none : nuclP.data(), offP.data(), (uint32_t) pre.c1, &orfP, &pre.O) != MK_OK) { pre.rc = EXIT_FAILURE; pre.err = mk_last_error(); return; }
                 const mk_orf *orfs; const uint64_t *aaOff; const char *aa;
                 mk_orfs_result(pre.O, &orfs, &aaOff, &aa, &pre.nb);
                 if (mk_queries_from_orfs(pre.O, &P, &pre.Q) != MK_OK) { pre.rc = EXIT_FAILURE; pre.err = mk_last_error(); }
@@ -1368,7 +1419,7 @@ int cmdPredictExons(int argc, char **argv) {
             const size_t c1 = contigBatchEnd(contigs, ord, c0);
             loadBatch(c0, c1);
             mk_orfs *O = nullptr;
-            if (mk_extract_orfs(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), minLength, &O) != MK_OK) return die("%s", mk_last_error());
+            if (mk_extract_orfs_ex(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), &orfP, &O) != MK_OK) return die("%s", mk_last_error());
             const mk_orf *orfs; const uint64_t *aaOff; const char *aa; uint64_t nb = 0;
             mk_orfs_result(O, &orfs, &aaOff, &aa, &nb);
             mine += nb;
@@ -1449,7 +1500,7 @@ int cmdPredictExons(int argc, char **argv) {
             loadBatch(c0, c1);
             double tb = now();
             tRead += tb - ta;
-            if (mk_extract_orfs(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), minLength, &b.O) != MK_OK) return die("%s", mk_last_error());
+            if (mk_extract_orfs_ex(nucl.empty() ? &none : nucl.data(), off.data(), (uint32_t) (c1 - c0), &orfP, &b.O) != MK_OK) return die("%s", mk_last_error());
             const mk_orf *orfs; const uint64_t *aaOff; const char *aa;
             mk_orfs_result(b.O, &orfs, &aaOff, &aa, &b.nb);
             if (mk_queries_from_orfs(b.O, &P, &b.Q) != MK_OK) return die("%s", mk_last_error());

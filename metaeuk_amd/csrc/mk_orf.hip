@@ -1,9 +1,11 @@
 // metaeuk_amd/csrc/mk_orf.hip -- six-frame ORF fragments of a batch of contigs, translated, on the GPU
-// (the producer of the hot path's queries).  Replaces, for `predictexons`' settings
-// (orf-start-mode 1, both strands, all frames, contig start/end mode 2, genetic code 1):
+// (the producer of the hot path's queries).  Replaces, for orf-start-mode 1, contig start mode 2 and
+// genetic code 1, with the frame masks, --max-gaps, --min-length / --max-length, --contig-end-mode and --reverse-fragments of the caller:
 //   Orf::setSequence / findAll / findForward    M/src/commons/Orf.cpp:118-345
 //   the extractorfs loop, --translate branch    M/src/util/extractorfs.cpp:64-125
 //   TranslateNucl::translate                    M/src/commons/TranslateNucl.h:488-503 (IUPAC-aware table: mk_host.cpp)
+//   reverseseq                                  M/src/util/reverseseq.cpp:41-47
+// The rule itself (Strand, stop_at, fragment_at, translate_at) is mk_orf_scan.hpp, shared with the host twin of mk_orf_host.cpp.
 // Layout: contigs stay as the caller's ASCII in HBM; nothing is copied or reverse-complemented -- the minus strand is an
 // index transform + complement lookup.  Three kernels:
 //   orf_mark_kernel          one lane per strand position: does a fragment end here, and how many codons has it
@@ -27,53 +29,15 @@ __constant__ char cComplement[256];
 __constant__ uint8_t cBaseCode[256];      // TranslateNucl::sm_BaseToIdx
 __constant__ uint8_t cAaCode[256];        // aa2num of the residue characters (mk::encode)
 
-struct Strand {
-    const char *seq; uint32_t len; bool minus;
-    // Orf::setSequence: only 'u' becomes 't' (the second assignment of the reference wins); minus strand = complement of
-    // the mirrored position, '.' -> 'N'; CHAR_MAX behind the end
-    __device__ __forceinline__ char at(uint32_t i) const {
-        if (i >= len) return (char) CHAR_MAX;
-        char c = seq[minus ? len - 1 - i : i];
-        if (c == 'u') c = 't';
-        if (minus) { c = cComplement[(unsigned char) c]; if (c == '.') c = 'N'; }
-        return c;
-    }
+// the tables of the shared rule (mk_orf_scan.hpp: Strand, stop_at, fragment_at, translate_at) as the kernels read them
+struct DevTab {
+    static __device__ __forceinline__ char complement(unsigned char c) { return cComplement[c]; }
+    static __device__ __forceinline__ uint8_t base_code(unsigned char c) { return cBaseCode[c]; }
 };
+typedef mk::Strand<DevTab> Strand;
 
-__device__ __forceinline__ char upper_or_max(char c) { return c == (char) CHAR_MAX ? c : (char) (c & (unsigned char) ~0x20); }
-__device__ __forceinline__ bool not_nucleotide(char c) { return c == 'N' || cComplement[(unsigned char) c] == '.'; }
-
-// With orf-start-mode 1 a fragment is a maximal stop-free codon run of one frame: it ENDS at a stop codon or at the last
-// complete codon of the frame, and STARTS three behind the previous stop of the frame (or at the frame offset: incomplete
-// start).  So every strand position decides on its own whether a fragment ends there (one lane per position, a short
-// backward walk to the previous stop), and the reference's output order -- contig, plus strand then minus strand, end
-// position ascending across the three frames -- is the order of the position index itself: ranks are a prefix sum.
-// (Orf::findForward's per-frame state machine, Orf.cpp:220-345; --max-gaps is the reference's default INT_MAX, i.e. off.)
-__device__ __forceinline__ bool stop_at(const Strand &S, uint32_t p) {
-    const char c0 = upper_or_max(S.at(p));
-    if (c0 != 'T') return false;
-    const char c1 = upper_or_max(S.at(p + 1)), c2 = upper_or_max(S.at(p + 2));
-    return (c1 == 'A' && (c2 == 'A' || c2 == 'G')) || (c1 == 'G' && c2 == 'A');
-}
-
-// fragment ending at strand position p (0 codons = none): start, length, flags
-__device__ __forceinline__ uint32_t fragment_at(const Strand &S, uint32_t p, uint32_t minLength, uint32_t maxLength, uint32_t &from, uint32_t &flags) {
-    if (S.len < 3 || p + 3 > S.len) return 0;                           // incomplete codon: never ends a fragment
-    const bool stop = stop_at(S, p);
-    const bool last = p + 6 > S.len;                                    // the frame's next codon is incomplete
-    if (!stop && !last) return 0;
-    uint32_t q = p;
-    bool hasStart = false;
-    while (q >= 3) {                                                    // previous stop of this frame
-        if (stop_at(S, q - 3)) { hasStart = true; break; }
-        q -= 3;
-    }
-    from = q;                                                           // = p % 3 when no stop precedes
-    const uint32_t count = (p - from) / 3 + (stop ? 0u : 1u);
-    if (count == 0 || count < minLength || count > maxLength) return 0;
-    flags = (hasStart ? 0u : 1u) | (stop ? 0u : 2u) | (S.minus ? 4u : 0u);
-    return count;
-}
+// One lane per strand position decides whether a fragment ends there (the rule and its per-position argument: mk_orf_scan.hpp); ranks are
+// a prefix sum over the positions, so positions, frames or whole strands that emit nothing leave the ranks dense.
 
 // virtual position index x = 2 * offsets[contig] + strand * len + p
 __device__ __forceinline__ bool locate(const OrfScanArgs &A, uint64_t x, uint32_t &contig, Strand &S, uint32_t &p) {
@@ -89,23 +53,27 @@ __device__ __forceinline__ bool locate(const OrfScanArgs &A, uint64_t x, uint32_
     return true;
 }
 
+// GAPS: the launch has a gap limit (--max-gaps below INT_MAX), and only then does the walk load whole codons and count; the default launch is
+// the <false> instance, whose walk loads the first character of a codon and the other two behind a T
+template <bool GAPS>
 __global__ __launch_bounds__(256) void orf_mark_kernel(OrfScanArgs A, uint64_t nPos, uint16_t *naa) {
     const uint64_t x = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= nPos) return;
     uint32_t contig, p, from, flags;
     Strand S;
     uint32_t n = 0;
-    if (locate(A, x, contig, S, p)) n = fragment_at(S, p, A.min_length, A.max_length, from, flags);
-    naa[x] = (uint16_t) n;                                              // <= 32734 codons
+    if (locate(A, x, contig, S, p)) n = fragment_at<GAPS>(S, p, A.rule, from, flags);
+    naa[x] = (uint16_t) n;                                              // <= 65535 codons (max_length)
 }
 
+template <bool GAPS>
 __global__ __launch_bounds__(256) void orf_write_kernel(OrfScanArgs A, uint64_t nPos, const uint16_t *naa, const uint64_t *rank, const uint64_t *aaBase) {
     const uint64_t x = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= nPos || naa[x] == 0) return;
     uint32_t contig, p, from = 0, flags = 0;
     Strand S;
     locate(A, x, contig, S, p);
-    const uint32_t n = fragment_at(S, p, A.min_length, A.max_length, from, flags);
+    const uint32_t n = fragment_at<GAPS>(S, p, A.rule, from, flags);
     OrfRecord r;
     r.contig = contig; r.s_from = from; r.n_aa = n; r.flags = flags;
     A.records[rank[x]] = r;
@@ -181,13 +149,11 @@ __global__ __launch_bounds__(256) void orf_translate_kernel(OrfScanArgs A, uint6
     const OrfRecord r = A.records[lo];
     Strand S;
     S.seq = A.nucl + A.offsets[r.contig]; S.len = (uint32_t) (A.offsets[r.contig + 1] - A.offsets[r.contig]); S.minus = (r.flags & 4u) != 0;
-    const uint32_t p = r.s_from + 3u * (uint32_t) (x - A.aa_off[lo]);
-    const char n0 = S.at(p), n1 = S.at(p + 1), n2 = S.at(p + 2);
-    char aa = sTable[256 * cBaseCode[(unsigned char) n0] + 16 * cBaseCode[(unsigned char) n1] + cBaseCode[(unsigned char) n2]];
-    const bool lower = (n0 >= 'a' && n0 <= 'z') || (n1 >= 'a' && n1 <= 'z') || (n2 >= 'a' && n2 <= 'z');
-    if (lower && aa >= 'A' && aa <= 'Z') aa = (char) (aa + 32);
-    aaAscii[x] = aa;
-    aaCode[x] = cAaCode[(unsigned char) aa];
+    const uint32_t i = (uint32_t) (x - A.aa_off[lo]);
+    const char aa = translate_at(S, r.s_from + 3u * i, sTable);
+    const uint64_t w = A.aa_off[lo] + orf_residue_slot(i, r.n_aa, A.rule.reverse);      // --reverse-fragments: the mirrored slot of the same fragment
+    aaAscii[w] = aa;
+    aaCode[w] = cAaCode[(unsigned char) aa];
 }
 
 bool g_tablesReady = false;
@@ -197,8 +163,8 @@ bool g_tablesReady = false;
 #define OCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return MK_ERR_DEVICE; } } while (0)
 #define ONULL(p) do { if (!(p)) { err = "device scratch allocation failed (" #p ")"; return MK_ERR_DEVICE; } } while (0)
 
-int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, uint32_t minLength, uint32_t maxLength, uint64_t maxGaps,
-                     hipStream_t stream, OrfDeviceResult &R, std::string &err) {
+int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, const OrfRule &rule, hipStream_t stream, OrfDeviceResult &R,
+                     std::string &err) {
     if (!g_tablesReady) {
         char comp[256]; uint8_t base[256], code[256];
         build_orf_tables(comp, base);
@@ -211,7 +177,7 @@ int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nCont
     R.n_frag = 0; R.n_aa = 0;
     if (nContigs == 0) return MK_OK;
     if (nContigs >= (1u << 30)) { err = "more than 2^30 contigs in one batch"; return MK_ERR_UNSUPPORTED; }
-    if (maxGaps < (uint64_t) INT_MAX) { err = "--max-gaps below the reference default (unlimited) is not implemented"; return MK_ERR_UNSUPPORTED; }
+    if (rule.max_length > 65535u) { err = "--max-length above 65535 codons: a fragment's length is kept in 16 bits"; return MK_ERR_UNSUPPORTED; }
     uint64_t *hTotals = (uint64_t *) pinned_scratch("orf_totals_h", 32);
     ONULL(hTotals);
     OCHK(hipMemcpyAsync(hTotals, dOffsets + nContigs, 8, hipMemcpyDeviceToHost, stream));
@@ -232,10 +198,12 @@ int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nCont
     }
     OrfScanArgs A;
     A.nucl = dNucl; A.offsets = dOffsets; A.n_contigs = nContigs;
-    A.min_length = minLength; A.max_length = maxLength; A.max_gaps = maxGaps;
+    A.rule = rule;
+    const bool gaps = orf_rule_counts_gaps(rule);                        // launch-uniform: which instance of the two walking kernels runs
     A.records = nullptr; A.aa_off = nullptr;
     const unsigned blocks = (unsigned) ((nPos + 255) / 256);
-    hipLaunchKernelGGL(orf_mark_kernel, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa);
+    if (gaps) hipLaunchKernelGGL(orf_mark_kernel<true>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa);
+    else hipLaunchKernelGGL(orf_mark_kernel<false>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa);
     OCHK(hipGetLastError());
     {
         const uint32_t sb = (uint32_t) ((nPos + ORF_SCAN_TILE - 1) / ORF_SCAN_TILE);
@@ -260,7 +228,8 @@ int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nCont
     R.aa_code = (uint8_t *) dev_block_alloc(std::max<uint64_t>(nAa, 1), &R.cap[3]);
     ONULL(R.records); ONULL(R.aa_off); ONULL(R.aa_ascii); ONULL(R.aa_code);
     A.records = R.records; A.aa_off = R.aa_off;
-    hipLaunchKernelGGL(orf_write_kernel, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
+    if (gaps) hipLaunchKernelGGL(orf_write_kernel<true>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
+    else hipLaunchKernelGGL(orf_write_kernel<false>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
     OCHK(hipGetLastError());
     OCHK(hipMemcpyAsync(R.aa_off + nFrag, dAaBase + nPos, 8, hipMemcpyDeviceToDevice, stream));
     hipLaunchKernelGGL(orf_translate_kernel, dim3((unsigned) ((nAa + 255) / 256)), dim3(256), 0, stream, A, nFrag, nAa, dTable, R.aa_ascii, R.aa_code);

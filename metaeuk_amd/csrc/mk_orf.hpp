@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include <vector>
 #include "../../include/metaeuk_amd.h"
 #include "mk_host.hpp"
+#include "mk_orf_scan.hpp"
 
 namespace mk {
 
@@ -14,7 +16,7 @@ struct OrfRecord { uint32_t contig; uint32_t s_from; uint32_t n_aa; uint32_t fla
 
 struct OrfScanArgs {
     const char *nucl; const uint64_t *offsets; uint32_t n_contigs;
-    uint32_t min_length, max_length; uint64_t max_gaps;              // codons (Orf::findAll's minLength / maxLength / maxGaps)
+    OrfRule rule;                                                    // Orf::findAll's arguments + the filter of the extractorfs loop
     OrfRecord *records; uint64_t *aa_off;
 };
 
@@ -27,7 +29,12 @@ struct OrfDeviceResult {
 };
 
 // contigs (ASCII, concatenated, offsets[n+1]) already in HBM -> fragments in the reference's output order
-int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, uint32_t minLength, uint32_t maxLength, uint64_t maxGaps,
-                     hipStream_t stream, OrfDeviceResult &R, std::string &err);
+int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, const OrfRule &rule, hipStream_t stream, OrfDeviceResult &R,
+                     std::string &err);
+
+// the same fragments on the host, no GPU call (mk_orf_host.cpp): the twin the kernels are checked against.  records / aaOff[n + 1] / aa / codes
+// are what the device call downloads.
+struct OrfHostResult { std::vector<OrfRecord> records; std::vector<uint64_t> aa_off; std::vector<char> aa; std::vector<uint8_t> codes; };
+void extract_orfs_host(const char *nucl, const uint64_t *offsets, uint32_t nContigs, const OrfRule &rule, OrfHostResult &out);
 
 }  // namespace mk
