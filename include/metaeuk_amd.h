@@ -98,6 +98,14 @@ typedef struct {
     int cov_mode;             /* --cov-mode    0: query and target, 1: target, 2: query, 3: target length >= x query length (and <= it),
                                  4: query length >= x target length (and <= it), 5: shorter length >= x longer length (Parameters.h:277-282) */
     float seq_id_thr;         /* --min-seq-id  0 .. 1 */
+    /* --max-accept / --max-rejected of the searchworkflow flag list (Alignment.cpp:343-405): the alignment stage walks a query's prefilter list in
+     * list order and stops once max_accept pairs were kept or max_rejected pairs IN A ROW were rejected (a pair that fails the length test of a
+     * result filter counts as rejected without being scored; a kept pair ends the streak).  The kept records are a prefix-determined subset of
+     * the unlimited run's, in the same order.  INT_MAX (the default) and 0 = no limit: the stage runs exactly as without the fields.  With a
+     * limit the stage works in rounds over growing windows of every open query's list and the pairs behind a stop are never scored.
+     * Negative: MK_ERR_ARG.  Not with profile queries / a profile database (the reference aligns twice there): MK_ERR_UNSUPPORTED. */
+    int max_accept;           /* --max-accept    >= 1; INT_MAX or 0: no limit */
+    int max_rejected;         /* --max-rejected  >= 1; INT_MAX or 0: no limit */
     int pad_;
     /* --alignment-mode / -a / --seq-id-mode of the searchworkflow flag list (Parameters.cpp; Alignment.cpp:35-37: -a turns the mode into 3).  All 0 =
      * today's Matcher::SCORE_COV: seq_id is the score-per-column estimate (Matcher.cpp:160-164), aln_len = max(q span, t span) + 1.  Mode 3
@@ -249,6 +257,19 @@ int mk_prefilter_result_set(mk_queries *q, const mk_hit *hits, const uint64_t *o
  * alignments, in output order, are alns[offsets[i] .. offsets[i+1]). */
 int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *params);
 int mk_align_result(const mk_queries *q, const mk_alignment **alns, const uint64_t **offsets /* n+1 */);
+/* what the alignment stage did for the batch in the last mk_align / mk_search: pairs in the prefilter lists, pairs that entered the score pass
+ * (without a limit: all but the pairs a result filter's length test removes), queries whose walk stopped at max_accept / at max_rejected, and
+ * score rounds (1 per chunk without a limit) */
+typedef struct { uint64_t pairs_listed, pairs_scored, stopped_accept, stopped_rejected, rounds; } mk_align_stats;
+int mk_align_statistics(const mk_queries *q, mk_align_stats *out);
+/* the --max-accept / --max-rejected rule on recorded verdicts, host code without a GPU and without mk_init (the twin the limit-scan kernel is
+ * checked against, and what the host assembly of the alignment stage decides with).  Query i owns verdicts[offsets[i] .. offsets[i+1]) in list
+ * order: 1 = accepted, 0 = rejected by the criteria, 2 = rejected by the length test.  keep_out[p] = 1 for the accepted pairs the reference keeps;
+ * looked_at_out[i] = pairs of query i the walk looked at.  state (may be NULL = a fresh walk): {passed, streak, stopped (0 open, 1 by accept,
+ * 2 by rejection)} per query, read and written -- a list fed in several runs gives the same answer.  Limits: >= 1, INT_MAX or 0 = none;
+ * negative MK_ERR_ARG. */
+int mk_align_limit_scan(const uint8_t *verdicts, const uint64_t *offsets, uint32_t n_queries, int max_accept, int max_rejected,
+                        uint32_t *state /* [n_queries][3] or NULL */, uint8_t *keep_out, uint32_t *looked_at_out /* [n_queries] or NULL */);
 /* the backtraces of a batch aligned with params->add_backtrace = 1 (mk_align or mk_search): alignment k of mk_align_result has
  * ops[ops_offsets[k] .. ops_offsets[k+1]), uncompressed M / I / D (empty for a pair without a path), and identities[k] identical residues.
  * Views owned by the batch handle.  MK_ERR_ARG when the batch was not aligned with add_backtrace. */

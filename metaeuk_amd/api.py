@@ -20,7 +20,8 @@ class Params(C.Structure):
                 ("evalue_thr", C.c_double), ("min_aln_len", C.c_int), ("simd_lanes_byte", C.c_int),
                 ("simd_lanes_word", C.c_int), ("simd_lanes_double", C.c_int), ("host_l2_bytes", C.c_uint64),
                 ("profile_search", C.c_int), ("kmer_size", C.c_int),
-                ("cov_thr", C.c_float), ("cov_mode", C.c_int), ("seq_id_thr", C.c_float), ("pad_", C.c_int),   # -c, --cov-mode, --min-seq-id
+                ("cov_thr", C.c_float), ("cov_mode", C.c_int), ("seq_id_thr", C.c_float),   # -c, --cov-mode, --min-seq-id
+                ("max_accept", C.c_int), ("max_rejected", C.c_int), ("pad_", C.c_int),   # --max-accept, --max-rejected (INT_MAX or 0: no limit)
                 ("alignment_mode", C.c_int), ("add_backtrace", C.c_int), ("seq_id_mode", C.c_int), ("pad2_", C.c_int)]   # --alignment-mode, -a, --seq-id-mode
 
 
@@ -53,7 +54,7 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_synth_targets", "mk_synth_fragments", "mk_synth_seqdb", "mk_synth_write_seqdb", "mk_targetdb_create_sequences", "mk_prefilter_statistics",
            "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size",
            "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band",
-           "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host"]
+           "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host", "mk_align_statistics", "mk_align_limit_scan"]
 
 
 def lib():
@@ -391,6 +392,15 @@ def prefilter_result(q):
     return raw.view(HIT_DTYPE), off
 
 
+def prefilter_result_set(q, hits, offsets):
+    """installs a prefilter result made elsewhere (mk_prefilter_result_set): hits = HIT_DTYPE array [total], offsets uint64[n+1]; copied"""
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(off) != q.n + 1 or int(off[-1]) != len(h):
+        raise ValueError("offsets: n + 1 entries ending at len(hits)")
+    _chk(lib().mk_prefilter_result_set(q.h, _p(h) if len(h) else None, _p(off)))
+
+
 ORF_DTYPE = np.dtype([("contig", "<u4"), ("from", "<u4"), ("to", "<u4"), ("incomplete_start", "u1"), ("incomplete_end", "u1"),
                       ("minus_strand", "u1"), ("pad_", "u1")])
 
@@ -589,6 +599,34 @@ def align_result(q):
         return (Alignment * 0)(), off
     alns = C.cast(ap, C.POINTER(Alignment * total)).contents
     return alns, off
+
+
+class AlignStats(C.Structure):
+    _fields_ = [("pairs_listed", C.c_uint64), ("pairs_scored", C.c_uint64), ("stopped_accept", C.c_uint64),
+                ("stopped_rejected", C.c_uint64), ("rounds", C.c_uint64)]
+
+
+def align_statistics(q):
+    """what the alignment stage did for the batch in the last align / search -> dict (mk_align_statistics)"""
+    st = AlignStats()
+    _chk(lib().mk_align_statistics(q.h, C.byref(st)))
+    return {k: int(getattr(st, k)) for k, _ in AlignStats._fields_}
+
+
+def align_limit_scan(verdicts, offsets, max_accept, max_rejected, state=None):
+    """--max-accept / --max-rejected on recorded verdicts (host code, no GPU): 1 = accepted, 0 = rejected, 2 = failed the length test.
+    -> (keep uint8[total], looked_at uint32[n]); `state` (uint32 [n, 3], optional) carries a walk from one run of pairs to the next"""
+    v = np.ascontiguousarray(verdicts, dtype=np.uint8)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(off) - 1
+    keep = np.zeros(max(1, len(v)), dtype=np.uint8)
+    looked = np.zeros(max(1, n), dtype=np.uint32)
+    if state is not None and (state.dtype != np.uint32 or state.shape != (n, 3) or not state.flags.c_contiguous):
+        raise ValueError("state: a C-contiguous uint32 array [n, 3]")
+    vv = v if len(v) else np.zeros(1, dtype=np.uint8)
+    _chk(lib().mk_align_limit_scan(_p(vv), _p(off), C.c_uint32(n), C.c_int(int(max_accept)), C.c_int(int(max_rejected)),
+                                   None if state is None else _p(state), _p(keep), _p(looked)))
+    return keep[:len(v)], looked[:n]
 
 
 def sw_pairs(db, q, q_idx, t_idx, with_start=True, params=None):

@@ -7,6 +7,7 @@
 #include "mk_filters.hpp"
 #include "mk_host.hpp"
 #include "mk_kernels.hpp"
+#include "mk_limits.hpp"
 #include "mk_orf.hpp"
 #include "mk_exons.hpp"
 #include "mk_indexfile.hpp"
@@ -311,6 +312,7 @@ struct mk_queries {
     // the backtraces of a batch aligned with add_backtrace (mk_align_backtrace): operations of alignment k = btOps[btOff[k] .. btOff[k+1]), in the
     // order of `alns`; appended chunk by chunk like the alignments (align_range, after wait_turn)
     std::vector<char> btOps; std::vector<uint64_t> btOff; std::vector<uint32_t> btIds; bool haveBt = false;
+    mk_align_stats alnStats = {0, 0, 0, 0, 0};   // what the alignment stage did for the batch (mk_align_statistics); the workers add under g_alnStatsMutex
     uint64_t btLeftBand = 0;         // pairs of the last alignment whose trace left the band (no path)
     struct SearchJob *job = nullptr; // mk_search_begin: the search in flight over this batch (mk_search_wait clears it)
     // (the profile images too -- ADVICE round 5: a hipFree of theirs in mk_queries_destroy synchronised the device under the batch in flight)
@@ -517,6 +519,7 @@ void mk_default_params(mk_params *p) {
     p->profile_search = 0;
     p->kmer_size = 0;
     p->cov_thr = 0.0f; p->cov_mode = 0; p->seq_id_thr = 0.0f; p->pad_ = 0;
+    p->max_accept = INT_MAX; p->max_rejected = INT_MAX;
     p->alignment_mode = 0; p->add_backtrace = 0; p->seq_id_mode = 0; p->pad2_ = 0;
 }
 
@@ -530,6 +533,34 @@ static int check_filters(const mk_params *P, bool profiles) {
         return fail(MK_ERR_ARG, "result filters out of range: -c %g --cov-mode %d --min-seq-id %g (thresholds in [0, 1], coverage modes 0 to 5)", (double) P->cov_thr, P->cov_mode, (double) P->seq_id_thr);
     if (profiles && (P->cov_thr > 0.0f || P->seq_id_thr > 0.0f || P->cov_mode != 0))
         return fail(MK_ERR_UNSUPPORTED, "-c / --cov-mode / --min-seq-id with profile queries (the inverted search of a profile target database) are not implemented");
+    return MK_OK;
+}
+
+// --max-accept / --max-rejected of a call: not negative; not for profile queries or a profile database (the reference aligns twice there,
+// searchslicedtargetprofile.sh, and the single pass of this build is only equivalent at the default limits)
+static bool limited(const mk_params *P) { return mk::limits_active(P->max_accept, P->max_rejected); }
+static int check_limits(const mk_params *P, bool profiles) {
+    if (P->max_accept < 0) return fail(MK_ERR_ARG, "--max-accept %d: a positive number is expected (INT_MAX or 0: no limit)", P->max_accept);
+    if (P->max_rejected < 0) return fail(MK_ERR_ARG, "--max-rejected %d: a positive number is expected (INT_MAX or 0: no limit)", P->max_rejected);
+    if (profiles && limited(P))
+        return fail(MK_ERR_UNSUPPORTED, "--max-accept / --max-rejected with profile queries (the inverted search of a profile target database) are not implemented");
+    return MK_OK;
+}
+
+int mk_align_limit_scan(const uint8_t *verdicts, const uint64_t *offsets, uint32_t nQueries, int maxAccept, int maxRejected, uint32_t *state,
+                        uint8_t *keepOut, uint32_t *lookedAtOut) {
+    if (!offsets || (!verdicts && offsets[nQueries] > 0) || (!keepOut && offsets[nQueries] > 0)) return fail(MK_ERR_ARG, "null argument");
+    if (maxAccept < 0 || maxRejected < 0) return fail(MK_ERR_ARG, "--max-accept %d --max-rejected %d: positive numbers are expected (INT_MAX or 0: no limit)", maxAccept, maxRejected);
+    const uint32_t mA = mk::limit_of(maxAccept), mR = mk::limit_of(maxRejected);
+    for (uint32_t i = 0; i < nQueries; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(MK_ERR_ARG, "offsets are not ascending at query %u", i);
+        mk::LimitState s{0, 0, mk::LIMIT_OPEN};
+        if (state) { s.passed = state[3 * (size_t) i]; s.streak = state[3 * (size_t) i + 1]; s.stopped = state[3 * (size_t) i + 2]; }
+        if (s.stopped > mk::LIMIT_STOP_REJECT) return fail(MK_ERR_ARG, "state of query %u: stopped = %u (0, 1 or 2)", i, s.stopped);
+        const uint64_t looked = mk::limit_step(s, verdicts + offsets[i], offsets[i + 1] - offsets[i], mA, mR, keepOut + offsets[i]);
+        if (lookedAtOut) lookedAtOut[i] = (uint32_t) looked;
+        if (state) { state[3 * (size_t) i] = s.passed; state[3 * (size_t) i + 1] = s.streak; state[3 * (size_t) i + 2] = s.stopped; }
+    }
     return MK_OK;
 }
 
@@ -567,6 +598,7 @@ int mk_result_filter(const mk_params *p, int q_len, int t_len, const mk_alignmen
     int rc = check_filters(p, false);
     if (rc != MK_OK) return rc;
     if ((rc = check_alignment_mode(p, false)) != MK_OK) return rc;
+    if ((rc = check_limits(p, false)) != MK_OK) return rc;
     if (!mk::can_be_covered(p->cov_thr, p->cov_mode, static_cast<float>(q_len), static_cast<float>(t_len))) return 0;
     if (a && !(mk::has_coverage(p->cov_thr, p->cov_mode, a->qcov, a->dbcov) && mk::seq_id_ok(a->seq_id, p->seq_id_thr))) return 0;
     return 1;
@@ -1612,14 +1644,23 @@ int mk_prefilter_result_set(mk_queries *q, const mk_hit *hits, const uint64_t *o
 // float/double tail (Matcher.cpp:60-142), Alignment::checkCriteria (:548-567) and the per-query sort (:403-405).
 // Appends the accepted alignments at alns[nAlnOut...] and fills alnOff[q0+1 .. q1].
 // (wait_turn: with several workers on one batch, called before anything of the batch's result block is touched -- chunks commit in order)
-static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint32_t q0, uint32_t q1, const std::vector<mk::GateEntry> &gate,
-                       const mk::AssembleTables *tables, hipStream_t stream, size_t &nAlnOut, const std::function<void()> &wait_turn = nullptr) {
+// --max-accept / --max-rejected: one round of the stage over the next window of every open query (align_range below).  The walk state is the
+// caller's; the round's kept records stay here, per query in compareHits order, until the last round has run
+struct LimitRound {
+    uint32_t *state = nullptr, *looked = nullptr;        // pinned, [queries of the range][3] / [queries of the range]
+    std::vector<mk_alignment> alns; std::vector<uint32_t> cnt;
+    std::vector<char> ops; std::vector<uint64_t> opsOff; std::vector<uint32_t> ids;     // -a: the operation strings of alns, in their order
+    uint64_t leftBand = 0;
+};
+static std::mutex g_alnStatsMutex;
+
+// (hitOff / hits / n: the pair list of the range -- the batch's prefilter result, or a round's windows)
+static int align_range_once(mk_targetdb *db, mk_queries *q, const mk_params *P, uint32_t q0, uint32_t q1, std::vector<uint64_t> &hitOff, const mk_hit *hits, size_t n,
+                            const std::vector<mk::GateEntry> &gate, const mk::AssembleTables *tables, hipStream_t stream, size_t &nAlnOut,
+                            const std::function<void()> &wait_turn, LimitRound *R, uint64_t *scoredOut) {
     const uint32_t nqc = q1 - q0;
-    const uint64_t h0 = q->hitOff[q0];
-    size_t n = (size_t) (q->hitOff[q1] - h0);
-    const mk_hit *hits = (const mk_hit *) q->hits.p + h0;
-    std::vector<uint64_t> hitOff((size_t) nqc + 1);            // pair offsets of the range
-    for (uint32_t i = 0; i <= nqc; i++) hitOff[i] = q->hitOff[(size_t) q0 + i] - h0;
+    const std::vector<uint64_t> listOff = R ? hitOff : std::vector<uint64_t>();     // (the host walk needs the window as it was handed over)
+    const mk_hit *listHits = hits;
     mk::AlignView V = align_view(db, q);
     V.q_off = q->dOff.p + q0; V.n_queries = nqc;
     V.co_resident = stream != g_stream;             // the alignment stage of mk_search runs beside the prefilter
@@ -1638,14 +1679,38 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
     if (!asmArgs.counts) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
     bool turned = false;
     const auto turn = [&]() { if (!turned && wait_turn) wait_turn(); turned = true; };
+    mk_alignment *roundDst = nullptr;
     asmArgs.reserve = [&](size_t cnt) -> mk_alignment * {
+        if (R) return roundDst = (mk_alignment *) mk::pinned_scratch("limit_round_alns", cnt * sizeof(mk_alignment));     // (a round's records wait for the merge)
         turn();
         if (!q->alns.reserve(std::max<size_t>(nAlnOut + cnt, 1) * sizeof(mk_alignment), nAlnOut * sizeof(mk_alignment))) return nullptr;
         return (mk_alignment *) q->alns.p + nAlnOut;
     };
+    const uint32_t maxAccept = mk::limit_of(P->max_accept), maxRejected = mk::limit_of(P->max_rejected);
+    if (R) { asmArgs.maxAccept = P->max_accept; asmArgs.maxRejected = P->max_rejected; asmArgs.limitState = R->state; asmArgs.limitLooked = R->looked; R->cnt.assign(nqc, 0); }
     int rc = mk::run_align_device(V, hitOff.data(), hits, n, gate, *P, stream, nullptr, &raw, &m, err, timed_begin, timed_end, timed_set, &asmArgs);
     timed_flush();
     if (rc != MK_OK) return fail(rc, "%s", err.c_str());
+    if (scoredOut) *scoredOut = asmArgs.cutPairs;
+    if (asmArgs.done && R) {
+        if (asmArgs.limitScanned) {
+            R->cnt.assign(asmArgs.counts, asmArgs.counts + nqc);
+            if (asmArgs.nOut) R->alns.assign(roundDst, roundDst + asmArgs.nOut);
+        } else {
+            // no pair of the round reached the assembly (nothing survived the length test or the e-value gate): every pair is a rejection
+            if (asmArgs.nOut != 0) return fail(MK_ERR_DEVICE, "internal: a round kept records without the limit scan");
+            std::vector<uint8_t> zero;
+            for (uint32_t i = 0; i < nqc; i++) {
+                const uint64_t w = listOff[i + 1] - listOff[i];
+                if (w == 0) continue;
+                if (zero.size() < w) zero.assign(w, mk::VERDICT_REJECTED);
+                mk::LimitState s{R->state[3 * (size_t) i], R->state[3 * (size_t) i + 1], R->state[3 * (size_t) i + 2]};
+                R->looked[i] = (uint32_t) mk::limit_step(s, zero.data(), w, maxAccept, maxRejected, nullptr);
+                R->state[3 * (size_t) i] = s.passed; R->state[3 * (size_t) i + 1] = s.streak; R->state[3 * (size_t) i + 2] = s.stopped;
+            }
+        }
+        return MK_OK;
+    }
     if (asmArgs.done) {
         turn();
         uint64_t o = 0;
@@ -1699,18 +1764,21 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
                                   tops.data(), stream, tres.data(), err, timed_begin, timed_end, &st);
         timed_flush();
         if (rc != MK_OK) return fail(rc, "%s", err.c_str());
-        turn();
-        q->btLeftBand += st.leftBand;
+        if (R) R->leftBand += st.leftBand;
+        else { turn(); q->btLeftBand += st.leftBand; }
     }
-    turn();
+    if (!R) turn();
     std::vector<uint32_t> src(mode3 ? m : 0);          // mode 3: the record behind every kept alignment
     // records are written at their upper-bound position; rejected ones (rare) leave holes that are closed afterwards
-    if (!q->alns.reserve(std::max<size_t>(nAlnOut + m, 1) * sizeof(mk_alignment), nAlnOut * sizeof(mk_alignment))) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
-    mk_alignment *alns = (mk_alignment *) q->alns.p + nAlnOut;
+    std::vector<mk_alignment> roundAlns(R ? std::max<size_t>(m, 1) : 0);      // (a round of a limited run: the records wait for the merge)
+    if (!R && !q->alns.reserve(std::max<size_t>(nAlnOut + m, 1) * sizeof(mk_alignment), nAlnOut * sizeof(mk_alignment))) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+    mk_alignment *alns = R ? roundAlns.data() : (mk_alignment *) q->alns.p + nAlnOut;
     std::vector<uint32_t> cnt(nqc);
-    int mismatch = 0;
+    std::vector<uint32_t> accPair(R ? m : 0);          // a limit: the pair (of the stage's list) behind every accepted record
+    const bool listCut = asmArgs.hitsCut != nullptr;
+    int mismatch = 0, walkBroken = 0;
     uint64_t holes = 0;
-#pragma omp parallel for schedule(dynamic, 512) reduction(+ : mismatch, holes)
+#pragma omp parallel for schedule(dynamic, 512) reduction(+ : mismatch, holes, walkBroken)
     for (uint32_t i = 0; i < nqc; i++) {
         const int qLen = (int) (q->off[(size_t) q0 + i + 1] - q->off[(size_t) q0 + i]);
         const uint64_t begin = first[i];
@@ -1743,7 +1811,32 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
             a.bit_score = static_cast<int>(db->evaluer.bitScore((double) r.score) + 0.5);
             if (a.evalue <= P->evalue_thr && a.aln_len >= P->min_aln_len && mk_result_filter(P, qLen, tLen, &a) == 1) {
                 if (mode3) src[w] = (uint32_t) k;
+                if (R) accPair[w] = r.pair;
                 alns[w++] = a;
+            }
+        }
+        if (R) {
+            // --max-accept / --max-rejected: the verdicts of the window in list order -- the pairs that failed the length test at their positions,
+            // never scored --, the walk (mk_limits.hpp), and the accepted records behind the stop go
+            const uint64_t w0 = listOff[i], nWin = listOff[i + 1] - w0;
+            std::vector<uint8_t> verdict(nWin, mk::VERDICT_REJECTED), keep(nWin, 0);
+            std::vector<uint32_t> posOf;                      // pair of the stage's list (counted from the query's first) -> position in the window
+            posOf.reserve(nWin);
+            for (uint64_t p = 0; p < nWin; p++) {
+                const uint32_t t = listHits[w0 + p].seq_id;
+                if (listCut && !mk::can_be_covered(P->cov_thr, P->cov_mode, (float) (uint32_t) qLen, (float) (uint32_t) (db->off[t + 1] - db->off[t]))) verdict[p] = mk::VERDICT_LENGTH;
+                else posOf.push_back((uint32_t) p);
+            }
+            if (posOf.size() != hitOff[i + 1] - hitOff[i]) walkBroken++;
+            else {
+                for (uint64_t x = begin; x < w; x++) verdict[posOf[accPair[x] - hitOff[i]]] = mk::VERDICT_ACCEPTED;
+                mk::LimitState s{R->state[3 * (size_t) i], R->state[3 * (size_t) i + 1], R->state[3 * (size_t) i + 2]};
+                R->looked[i] = (uint32_t) mk::limit_step(s, verdict.data(), nWin, maxAccept, maxRejected, keep.data());
+                R->state[3 * (size_t) i] = s.passed; R->state[3 * (size_t) i + 1] = s.streak; R->state[3 * (size_t) i + 2] = s.stopped;
+                uint64_t w2 = begin;
+                for (uint64_t x = begin; x < w; x++)
+                    if (keep[posOf[accPair[x] - hitOff[i]]]) { alns[w2] = alns[x]; if (mode3) src[w2] = src[x]; w2++; }
+                w = w2;
             }
         }
         if (mode3 && w - begin > 1) {                         // the same order, the records' sources carried along
@@ -1768,12 +1861,28 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
         holes += first[i + 1] - w;
     }
     if (mismatch) return fail(MK_ERR_SW_MISMATCH, "Score of forward/backward SW differ for %d pairs", mismatch);
+    if (walkBroken) return fail(MK_ERR_DEVICE, "internal: the length cut of the stage and of the limit walk disagree for %d queries", walkBroken);
     uint64_t o = 0;                                    // range-local offsets
     for (uint32_t i = 0; i < nqc; i++) {
         if (holes && cnt[i] && o != first[i]) std::memmove(alns + o, alns + first[i], (size_t) cnt[i] * sizeof(mk_alignment));   // blocks only move forward
         if (mode3 && holes && cnt[i] && o != first[i]) std::memmove(src.data() + o, src.data() + first[i], (size_t) cnt[i] * sizeof(uint32_t));
         o += cnt[i];
-        q->alnOff[(size_t) q0 + i + 1] = nAlnOut + o;
+        if (!R) q->alnOff[(size_t) q0 + i + 1] = nAlnOut + o;
+    }
+    if (R) {
+        R->cnt = cnt;
+        R->alns.assign(alns, alns + o);
+        if (keepOps) {
+            R->opsOff.assign(1, 0);
+            for (uint64_t x = 0; x < o; x++) {
+                const int64_t j = jobOf[src[x]];
+                const bool path = j >= 0 && tres[(size_t) j].status == mk::TRACE_OK;
+                if (path) R->ops.insert(R->ops.end(), tops.begin() + (ptrdiff_t) topsOff[(size_t) j], tops.begin() + (ptrdiff_t) (topsOff[(size_t) j] + tres[(size_t) j].bt_len));
+                R->opsOff.push_back(R->ops.size());
+                R->ids.push_back(path ? tres[(size_t) j].identities : 0u);
+            }
+        }
+        return MK_OK;
     }
     if (keepOps) {                                     // the strings in the order of the alignments (the chunk's turn: appended in chunk order)
         if (q->btOff.empty()) q->btOff.push_back(0);
@@ -1789,6 +1898,120 @@ static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint3
     return MK_OK;
 }
 
+// The window schedule of a limited run: the first window holds min(max_accept, max_rejected) pairs -- no walk can stop sooner --, 8 at least
+// (a wave of the score pass carries 8 to 32 DPs of one query; a narrower window idles its lanes and still costs a round of launches), and
+// every further round doubles it: a list of n pairs is through after log2(n / 8) rounds, and a query scores less than twice the pairs its
+// walk looked at (plus the first window).  MK_ALIGN_LIMIT_WINDOW (MK_DEBUG=1) fixes the window at that many pairs for every round.
+static uint64_t limit_first_window(const mk_params *P) {
+    return std::min<uint64_t>(1u << 30, std::max<uint64_t>(8, std::min(mk::limit_of(P->max_accept), mk::limit_of(P->max_rejected))));
+}
+
+static int align_range(mk_targetdb *db, mk_queries *q, const mk_params *P, uint32_t q0, uint32_t q1, const std::vector<mk::GateEntry> &gate,
+                       const mk::AssembleTables *tables, hipStream_t stream, size_t &nAlnOut, const std::function<void()> &wait_turn = nullptr) {
+    const uint32_t nqc = q1 - q0;
+    const uint64_t h0 = q->hitOff[q0];
+    const size_t n = (size_t) (q->hitOff[q1] - h0);
+    const mk_hit *hits = (const mk_hit *) q->hits.p + h0;
+    std::vector<uint64_t> hitOff((size_t) nqc + 1);            // pair offsets of the range
+    for (uint32_t i = 0; i <= nqc; i++) hitOff[i] = q->hitOff[(size_t) q0 + i] - h0;
+    mk_align_stats st = {n, 0, 0, 0, 0};
+    const auto add_stats = [&]() {
+        std::lock_guard<std::mutex> g(g_alnStatsMutex);
+        q->alnStats.pairs_listed += st.pairs_listed; q->alnStats.pairs_scored += st.pairs_scored; q->alnStats.stopped_accept += st.stopped_accept;
+        q->alnStats.stopped_rejected += st.stopped_rejected; q->alnStats.rounds += st.rounds;
+    };
+    if (!limited(P)) {
+        uint64_t scored = 0;
+        const int rc = align_range_once(db, q, P, q0, q1, hitOff, hits, n, gate, tables, stream, nAlnOut, wait_turn, nullptr, &scored);
+        st.pairs_scored = scored; st.rounds = 1;
+        if (rc == MK_OK) add_stats();
+        return rc;
+    }
+    // ---- --max-accept / --max-rejected: rounds over the next window of every open query
+    const bool keepOps = P->add_backtrace == 1;
+    uint32_t *state = (uint32_t *) mk::pinned_scratch("limit_walk_state", std::max<size_t>(nqc, 1) * 12);
+    uint32_t *looked = (uint32_t *) mk::pinned_scratch("limit_walk_looked", std::max<size_t>(nqc, 1) * 4);
+    if (!state || !looked) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+    std::memset(state, 0, (size_t) nqc * 12);
+    const long fixedWindow = mk::knob_long("MK_ALIGN_LIMIT_WINDOW", 0);
+    uint64_t window = fixedWindow > 0 ? (uint64_t) fixedWindow : limit_first_window(P);
+    std::vector<uint64_t> pos(nqc, 0), winOff((size_t) nqc + 1);
+    std::vector<LimitRound> rounds;
+    for (;;) {
+        winOff[0] = 0;
+        for (uint32_t i = 0; i < nqc; i++) {
+            const uint64_t left = hitOff[i + 1] - hitOff[i] - pos[i];
+            winOff[i + 1] = winOff[i] + (state[3 * (size_t) i + 2] == mk::LIMIT_OPEN ? std::min(left, window) : 0);
+        }
+        const size_t total = (size_t) winOff[nqc];
+        if (total == 0) break;
+        mk_hit *winHits = (mk_hit *) mk::pinned_scratch("limit_window_hits", total * sizeof(mk_hit));
+        if (!winHits) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+#pragma omp parallel for schedule(static)
+        for (uint32_t i = 0; i < nqc; i++)
+            if (winOff[i + 1] > winOff[i]) std::memcpy(winHits + winOff[i], hits + hitOff[i] + pos[i], (size_t) (winOff[i + 1] - winOff[i]) * sizeof(mk_hit));
+        for (uint32_t i = 0; i < nqc; i++) pos[i] += winOff[i + 1] - winOff[i];
+        std::memset(looked, 0, (size_t) nqc * 4);
+        rounds.emplace_back();
+        LimitRound &R = rounds.back();
+        R.state = state; R.looked = looked;
+        uint64_t scored = 0;
+        std::vector<uint64_t> roundOff = winOff;                 // (a result filter leaves the offsets of its own list in there)
+        const int rc = align_range_once(db, q, P, q0, q1, roundOff, winHits, total, gate, tables, stream, nAlnOut, wait_turn, &R, &scored);
+        if (rc != MK_OK) return rc;
+        st.pairs_scored += scored; st.rounds++;
+        if (fixedWindow <= 0) window = std::min<uint64_t>(window * 2, 1u << 30);
+    }
+    for (uint32_t i = 0; i < nqc; i++) { st.stopped_accept += state[3 * (size_t) i + 2] == mk::LIMIT_STOP_ACCEPT; st.stopped_rejected += state[3 * (size_t) i + 2] == mk::LIMIT_STOP_REJECT; }
+    // a query's records of all rounds, contiguous and in compareHits order (Alignment.cpp:403-405: one sort over everything the walk kept)
+    size_t total = 0;
+    for (const LimitRound &R : rounds) total += R.alns.size();
+    if (wait_turn) wait_turn();
+    if (!q->alns.reserve(std::max<size_t>(nAlnOut + total, 1) * sizeof(mk_alignment), nAlnOut * sizeof(mk_alignment))) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+    mk_alignment *alns = (mk_alignment *) q->alns.p + nAlnOut;
+    std::vector<size_t> at(rounds.size(), 0);                    // the next record of every round
+    struct Src { uint32_t round; size_t idx; };
+    std::vector<Src> from;
+    if (keepOps && q->btOff.empty()) q->btOff.push_back(0);
+    size_t o = 0;
+    for (uint32_t i = 0; i < nqc; i++) {
+        const size_t begin = o;
+        from.clear();
+        int parts = 0;
+        for (size_t r = 0; r < rounds.size(); r++) {
+            const uint32_t c = rounds[r].cnt[i];
+            if (c == 0) continue;
+            parts++;
+            for (uint32_t x = 0; x < c; x++) { alns[o++] = rounds[r].alns[at[r] + x]; from.push_back(Src{(uint32_t) r, at[r] + x}); }
+            at[r] += c;
+        }
+        if (parts > 1) {
+            std::vector<uint32_t> perm(o - begin);
+            for (size_t x = 0; x < perm.size(); x++) perm[x] = (uint32_t) x;
+            std::sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
+                mk_alignment kx = alns[begin + x], ky = alns[begin + y];
+                if (!db->keys.empty()) { kx.db_key = db->keys[kx.db_key]; ky.db_key = db->keys[ky.db_key]; }
+                return mk::alignment_less(kx, ky);
+            });
+            const std::vector<mk_alignment> ta(alns + begin, alns + o);
+            const std::vector<Src> tf = from;
+            for (size_t x = 0; x < perm.size(); x++) { alns[begin + x] = ta[perm[x]]; from[x] = tf[perm[x]]; }
+        }
+        if (keepOps)
+            for (const Src &f : from) {
+                const LimitRound &R = rounds[f.round];
+                q->btOps.insert(q->btOps.end(), R.ops.begin() + (ptrdiff_t) R.opsOff[f.idx], R.ops.begin() + (ptrdiff_t) R.opsOff[f.idx + 1]);
+                q->btOff.push_back(q->btOps.size());
+                q->btIds.push_back(R.ids[f.idx]);
+            }
+        q->alnOff[(size_t) q0 + i + 1] = nAlnOut + o;
+    }
+    for (const LimitRound &R : rounds) q->btLeftBand += R.leftBand;
+    nAlnOut += o;
+    add_stats();
+    return MK_OK;
+}
+
 int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     int rc = ensure_ready();
     if (rc) return rc;
@@ -1797,7 +2020,9 @@ int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if ((rc = check_roles(db, q)) != MK_OK) return rc;
     if ((rc = check_filters(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
     if ((rc = check_alignment_mode(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
+    if ((rc = check_limits(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
     q->btOps.clear(); q->btOff.clear(); q->btIds.clear(); q->haveBt = false; q->btLeftBand = 0;
+    q->alnStats = mk_align_stats{0, 0, 0, 0, 0};
     HostTimer htAll("host_align_total");
     std::shared_ptr<const ScoreTabs> tabs;
     {
@@ -2056,7 +2281,9 @@ int mk_search_begin(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if ((rc = check_roles(db, q)) != MK_OK) return rc;
     if ((rc = check_filters(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
     if ((rc = check_alignment_mode(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
+    if ((rc = check_limits(P, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
     q->btOps.clear(); q->btOff.clear(); q->btIds.clear(); q->haveBt = false; q->btLeftBand = 0;
+    q->alnStats = mk_align_stats{0, 0, 0, 0, 0};
     SearchJob *job = new SearchJob();
     job->db = db; job->q = q; job->P = *P;
     job->hostThreads = omp_get_max_threads();
@@ -2115,6 +2342,13 @@ int mk_align_result(const mk_queries *q, const mk_alignment **alns, const uint64
     if (!q || !alns || !offsets) return fail(MK_ERR_ARG, "null argument");
     if (!q->haveAln) return fail(MK_ERR_ARG, "no alignment result in this batch");
     *alns = (const mk_alignment *) q->alns.p; *offsets = q->alnOff.data();
+    return MK_OK;
+}
+
+int mk_align_statistics(const mk_queries *q, mk_align_stats *out) {
+    if (!q || !out) return fail(MK_ERR_ARG, "null argument");
+    if (!q->haveAln) return fail(MK_ERR_ARG, "no alignment result in this batch");
+    *out = q->alnStats;
     return MK_OK;
 }
 

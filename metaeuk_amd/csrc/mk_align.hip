@@ -22,9 +22,15 @@
 //   rev_jobs_kernel<true>    a survivor whose coverage over (0, end cell) misses the threshold gets no reverse job
 //                            (StripedSmithWaterman.cpp:389-398); collect_kernel marks it (q_start == ALN_SKIPPED)
 //   assemble_kernel          the final coverage and the sequence identity join the criteria (Alignment.cpp:548-567)
+// With --max-accept / --max-rejected (mk_limits.hpp) the caller hands over the next WINDOW of every open query's list, round by round, and two
+// kernels run behind the last criterion and in front of the per-query sort (nothing of this runs at the default limits):
+//   limit_mark_kernel        accepted record -> its pair
+//   limit_scan_kernel        one wave per query walks the window in list order from the carried state (ballots, Alignment.cpp:343-397); the
+//                            records behind the stop lose their pass flag, so they never reach the sort or the output
 #include "mk_align.hpp"
 #include "mk_filters.hpp"
 #include "mk_kernels.hpp"
+#include "mk_limits.hpp"
 #include "mk_segsort.hpp"
 #include <algorithm>
 #include <cmath>
@@ -471,6 +477,52 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleView A) {
                  seq_id_ok(a.seq_id, A.filter.seq_id_thr)) ? 1 : 0;
 }
 
+// ---- --max-accept / --max-rejected ------------------------------------------------------------------------------------------------
+constexpr uint32_t LIMIT_NO_RECORD = 0xFFFFFFFFu;
+// pairRec[pair of the stage's list] = the record that passed every criterion (LIMIT_NO_RECORD, set by the host, for every other pair)
+__global__ __launch_bounds__(256) void limit_mark_kernel(const AlnRaw *raw, const uint8_t *pass, uint32_t n, uint32_t nPairs, uint32_t *pairRec) {
+    helper_prio();
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n && pass[k] && raw[k].pair < nPairs) pairRec[raw[k].pair] = k;
+}
+// One wave per query.  The window is the caller's list (hitOff / hits); with a result filter the stage scored a compacted copy of it (cutOff: the
+// first pair of every query there) -- the pairs that fail the length test are seen here at their list positions, as rejections, and the others
+// find their record through their number among the query's surviving pairs (the same predicate and the same ballot as cut_emit_kernel).
+// 64 pairs per step: accepted mask by ballot, every lane asks whether the walk would stop behind its pair (mk_limits.hpp: a population count and
+// a count of leading zeros), a second ballot gives the first such lane.  The steps behind a stop only clear flags.
+__global__ __launch_bounds__(256) void limit_scan_kernel(AlignView V, const uint64_t *hitOff, const mk_hit *hits, bool filtered, ResultFilter F,
+                                                         const uint64_t *cutOff, uint32_t nCutPairs, const uint32_t *pairRec, uint8_t *pass, uint32_t nRec,
+                                                         uint32_t maxAccept, uint32_t maxRejected, uint32_t *state /* [nq][3] */, uint32_t *looked /* [nq] */) {
+    helper_prio();
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (q >= V.n_queries) return;
+    const uint64_t p0 = hitOff[q], p1 = hitOff[q + 1];
+    LimitState s{state[3 * (size_t) q], state[3 * (size_t) q + 1], state[3 * (size_t) q + 2]};
+    const float qLen = (float) (uint32_t) (V.q_off[q + 1] - V.q_off[q]);
+    uint64_t c = filtered ? cutOff[q] : p0;              // the next surviving pair of the query in the stage's list
+    uint32_t lookedAll = 0;
+    for (uint64_t b = p0; b < p1; b += 64) {
+        const uint64_t p = b + lane;
+        bool scored = false;
+        if (p < p1) {
+            const uint32_t t = hits[p].seq_id;
+            scored = !filtered || t >= V.n_targets || can_be_covered(F.cov_thr, F.cov_mode, qLen, (float) (uint32_t) (V.t_off[t + 1] - V.t_off[t]));
+        }
+        const unsigned long long m = __ballot(scored);
+        const uint64_t ci = c + (uint32_t) __popcll(m & ((1ull << lane) - 1ull));
+        uint32_t rec = LIMIT_NO_RECORD;
+        if (scored && ci < nCutPairs) rec = pairRec[ci];
+        const bool accepted = rec < nRec;
+        const uint64_t acc = __ballot(accepted);
+        const uint32_t n = (uint32_t) min((uint64_t) 64, p1 - b);
+        const uint64_t stop = __ballot(lane < n && s.stopped == LIMIT_OPEN && limit_lane_stops(s, acc, lane, maxAccept, maxRejected));
+        uint64_t kept;
+        lookedAll += limit_finish(s, acc, n, stop, kept);          // (wave-uniform: every lane moves the same state)
+        if (accepted && !((kept >> lane) & 1ull)) pass[rec] = 0;
+        c += (uint32_t) __popcll(m);
+    }
+    if (lane == 0) { state[3 * (size_t) q] = s.passed; state[3 * (size_t) q + 1] = s.streak; state[3 * (size_t) q + 2] = s.stopped; looked[q] = lookedAll; }
+}
 
 // one lane per query: its records are raw[first .. next) (raw is ordered by pair = by query): how many pass
 __global__ __launch_bounds__(256) void assemble_count_kernel(AssembleView A, uint32_t *cnt) {
@@ -866,7 +918,7 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
                      const AlnRaw **out, size_t *nOut, std::string &err, timed_begin_fn tb, timed_end_fn te, timed_set_fn ts,
                      AssembleArgs *assemble) {
     *out = nullptr; *nOut = 0;
-    if (assemble) { assemble->done = assemble->tables != nullptr; assemble->nOut = 0; if (assemble->counts) std::fill(assemble->counts, assemble->counts + V.n_queries, 0u); }
+    if (assemble) { assemble->done = assemble->tables != nullptr; assemble->nOut = 0; assemble->limitScanned = false; if (assemble->counts) std::fill(assemble->counts, assemble->counts + V.n_queries, 0u); }
     if (nPairs == 0) return MK_OK;
     if (nPairs >= 0x7FFFFFFFull) { err = "more than 2^31 pairs in one batch: split the batch"; return MK_ERR_UNSUPPORTED; }
     if (assemble) { assemble->cutPairs = nPairs; assemble->hitOffCut = nullptr; assemble->hitsCut = nullptr; }
@@ -894,6 +946,7 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
     ACHK(hipMemsetAsync(dFwdWork, 0, 2 * SW_NCFG * 8, stream));
     const ResultFilter F = result_filter_of(P);
     const bool filtered = filters_active(F);
+    const uint64_t *dHitOffList = dHitOff; const mk_hit *dHitsList = dHits;      // the caller's list (the limit scan walks it; a result filter moves on to a copy)
     uint32_t *hCount = (uint32_t *) pinned_scratch("align_count_h", 16);
     ANULL(hCount);
     int th;
@@ -1041,6 +1094,24 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
         AV.evalThr = P.evalue_thr; AV.minAlnLen = P.min_aln_len; AV.filter = F; AV.tmp = dTmp; AV.pass = dPass; AV.flags = dFlags;
         th = tb("align_assemble", (double) nRev * (sizeof(AlnRaw) + 2.0 * sizeof(mk_alignment)), 0);
         hipLaunchKernelGGL(assemble_kernel, dim3((nRev + 255) / 256), dim3(256), 0, stream, AV);
+        const bool limitRun = limits_active(assemble->maxAccept, assemble->maxRejected);
+        uint32_t *dLimState = nullptr;
+        if (limitRun) {
+            // --max-accept / --max-rejected: behind the last criterion, in front of the count and the sort
+            if (!assemble->limitState || !assemble->limitLooked) { err = "internal: a limit needs the caller's walk state"; return MK_ERR_ARG; }
+            const uint32_t nq = V.n_queries;
+            uint32_t *dPairRec = (uint32_t *) dev_scratch("limit_pairrec", (size_t) n * 4);
+            dLimState = (uint32_t *) dev_scratch("limit_state", (size_t) nq * 4 * 4);          // [nq][3] state, [nq] pairs looked at
+            ANULL(dPairRec); ANULL(dLimState);
+            ACHK(hipMemsetAsync(dPairRec, 0xFF, (size_t) n * 4, stream));
+            ACHK(hipMemcpyAsync(dLimState, assemble->limitState, (size_t) nq * 12, hipMemcpyHostToDevice, stream));
+            const int tl = tb("align_limit_scan", 4.0 * n + 16.0 * nq, 0);
+            hipLaunchKernelGGL(limit_mark_kernel, dim3((nRev + 255) / 256), dim3(256), 0, stream, (const AlnRaw *) dRaw, (const uint8_t *) dPass, nRev, n, dPairRec);
+            hipLaunchKernelGGL(limit_scan_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, V, dHitOffList, dHitsList, filtered, F, (const uint64_t *) dHitOff, n,
+                               (const uint32_t *) dPairRec, dPass, nRev, limit_of(assemble->maxAccept), limit_of(assemble->maxRejected), dLimState, dLimState + 3 * (size_t) nq);
+            te(tl);
+            ACHK(hipGetLastError());
+        }
         hipLaunchKernelGGL(assemble_count_kernel, dim3((V.n_queries + 255) / 256), dim3(256), 0, stream, AV, dCnt);
         ACHK(hipGetLastError());
         if ((rc = device_scan(dCnt, V.n_queries, dOff, dOff + V.n_queries, stream, err)) != MK_OK) return rc;
@@ -1052,7 +1123,18 @@ int run_align_device(const AlignView &V, const uint64_t *hitOffHost, const mk_hi
         ACHK(hipMemcpyAsync(hFlags + 2, dOff + V.n_queries, 4, hipMemcpyDeviceToHost, stream));
         ACHK(hipMemcpyAsync(assemble->counts, dCnt, (size_t) V.n_queries * 4, hipMemcpyDeviceToHost, stream));
         ACHK(hipMemcpyAsync(hCount, dCount, 12, hipMemcpyDeviceToHost, stream));
+        uint32_t *hLimState = nullptr;
+        if (limitRun) {                              // (into pinned scratch: the caller's state only moves when the range was assembled here)
+            hLimState = (uint32_t *) pinned_scratch("limit_state_h", (size_t) V.n_queries * 16);
+            ANULL(hLimState);
+            ACHK(hipMemcpyAsync(hLimState, dLimState, (size_t) V.n_queries * 16, hipMemcpyDeviceToHost, stream));
+        }
         ACHK(sync_wait(stream, "wait_align"));
+        if (limitRun && hFlags[0] == 0) {
+            std::memcpy(assemble->limitState, hLimState, (size_t) V.n_queries * 12);
+            std::memcpy(assemble->limitLooked, hLimState + 3 * (size_t) V.n_queries, (size_t) V.n_queries * 4);
+            assemble->limitScanned = true;
+        }
         if (hCount[2] != 0) { err = "internal: the position pass disagrees with the score pass for " + std::to_string(hCount[2]) + " pairs"; return MK_ERR_DEVICE; }
         if (hFlags[1] != 0) { err = "Score of forward/backward SW differ for " + std::to_string(hFlags[1]) + " pairs"; return MK_ERR_SW_MISMATCH; }
         if (hFlags[0] == 0) {

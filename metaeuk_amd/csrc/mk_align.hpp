@@ -61,6 +61,14 @@ struct AssembleArgs {
     // valid until the next call (null without a filter: the caller's own list)
     uint64_t cutPairs = 0;                       // pairs that went into the score pass
     const uint64_t *hitOffCut = nullptr; const mk_hit *hitsCut = nullptr;
+    // --max-accept / --max-rejected (mk_limits.hpp; 0 or INT_MAX: no limit, nothing of this is read).  The list handed over is the next window of
+    // every open query; the limit-scan kernel walks it from the carried state behind the last criterion of the device assembly, and the records
+    // behind a stop never reach the sort.  limitScanned == false after the call: the kernel did not run (no pair reached the assembly, or the
+    // caller assembles the range) and the caller walks the window with the host twin.
+    int maxAccept = 0, maxRejected = 0;
+    uint32_t *limitState = nullptr;              // host [n_queries][3]: {passed, streak, stopped}, read and written
+    uint32_t *limitLooked = nullptr;             // host [n_queries]: pairs of the window the walk looked at
+    bool limitScanned = false;
 };
 
 // pairs = (query of pair p is the one whose hitOff range contains p, target hits[p].seq_id); hits on the host.

@@ -63,7 +63,7 @@ const Flag FLAGS[] = {
     {"--taxon-list", "", false}, {"--threads", "", true}, {"--compressed", "0", false}, {"-v", "3", true},
     {"-a", "0", true}, {"--alignment-mode", "2", true}, {"--alignment-output-mode", "0", true}, {"--wrapped-scoring", "0", false},
     {"-e", "100", true}, {"--min-seq-id", "0", true}, {"--min-aln-len", "0", true}, {"--seq-id-mode", "0", true},
-    {"--alt-ali", "0", false}, {"--max-rejected", "2147483647", false}, {"--max-accept", "2147483647", false},
+    {"--alt-ali", "0", false}, {"--max-rejected", "2147483647", true}, {"--max-accept", "2147483647", true},
     {"--score-bias", "0", false}, {"--realign", "0", false}, {"--realign-score-bias", "-0.2", false}, {"--realign-max-seqs", "2147483647", false},
     {"--corr-score-weight", "0", false}, {"--gap-open", "aa:11,nucl:5", true}, {"--gap-extend", "aa:1,nucl:2", true}, {"--zdrop", "40", false},
     // predictexons only: extractorfs (Parameters.cpp:2525-2554), search workflow extras, collectoptimalset (LocalParameters.h:92-104)
@@ -202,6 +202,15 @@ int fillParams(const Args &a, mk_params &P, int &gpu) {
         if (*v != "0" && *v != "1" && *v != "2") return die("--seq-id-mode %s: 0 (alignment length), 1 (shorter sequence) and 2 (longer sequence) exist", *v);
         P.seq_id_mode = atoi(v->c_str());
     }
+    // --max-accept / --max-rejected (Alignment.cpp:343-405): the reference's pattern is ^[1-9]{1}[0-9]*$, so 0 is not a value of either flag
+    for (const char *k : {"--max-accept", "--max-rejected"})
+        if (auto v = get(k)) {
+            bool ok = !v->empty() && (*v)[0] >= '1' && (*v)[0] <= '9' && v->size() <= 10;
+            for (char c : *v) ok = ok && c >= '0' && c <= '9';
+            const long long x = ok ? atoll(v->c_str()) : 0;
+            if (!ok || x > 2147483647LL) return die((std::string(k) + " %s: a positive integer (at most 2147483647) is expected").c_str(), *v);
+            (k[6] == 'a' ? P.max_accept : P.max_rejected) = (int) x;
+        }
     if (auto v = get("--gap-open")) P.gap_open = atoi(aaPart(*v).c_str());
     if (auto v = get("--gap-extend")) P.gap_extend = atoi(aaPart(*v).c_str());
     if (auto v = get("--threads")) setenv("OMP_NUM_THREADS", v->c_str(), 0);
@@ -229,6 +238,9 @@ int refuseFiltersForProfiles(const mk_params &P) {
     if (P.alignment_mode == 3) return die("--alignment-mode 3: only mode 2 is implemented with profile targets%s");
     if (P.add_backtrace != 0) return die("-a: only the default (0) is implemented with profile targets%s");
     if (P.seq_id_mode != 0) return die("--seq-id-mode: only the default (0) is implemented with profile targets%s");
+    // ... and the reference aligns twice there (searchslicedtargetprofile.sh): the single pass of this build is only equivalent at the default limits
+    if (P.max_accept != 2147483647) return die("--max-accept: only the default (2147483647) is implemented with profile targets%s");
+    if (P.max_rejected != 2147483647) return die("--max-rejected: only the default (2147483647) is implemented with profile targets%s");
     return 0;
 }
 
