@@ -58,8 +58,27 @@ def encode(s):
 _ALN = None
 
 
-def sw(q, t, lanes_byte=32, lanes_word=16, gap_open=11, gap_extend=1, with_start=True):
-    """oracle SW for two amino-acid strings -> (score, q_end, t_end, q_start, t_start)"""
+def aln_matrix():
+    """the alignment matrix (BLOSUM62, bit factor 2) as the kernels read it: int8 [21, 21]"""
+    global _ALN
+    if _ALN is None:
+        _ALN = submat(0, 2.0, 0.0)
+    return np.array([[_ALN.sub[i][j] for j in range(21)] for i in range(21)], dtype=np.int16).astype(np.int8)
+
+
+def query_bias8(q, bias_scale=1.0):
+    """the int8 composition bias of a query's rows (ssw_init) at the given scale; 0: no correction"""
+    aln_matrix()
+    qc = encode(q)
+    cb = np.zeros(max(1, len(q)), dtype=np.int8)
+    bias = C.c_int()
+    lib().mko_sw_query_init(C.byref(_ALN), qc.ctypes.data_as(C.c_void_p), C.c_int(len(q)), C.c_float(bias_scale), cb.ctypes.data_as(C.c_void_p), C.byref(bias))
+    return cb[:len(q)]
+
+
+def sw(q, t, lanes_byte=32, lanes_word=16, gap_open=11, gap_extend=1, with_start=True, bias_scale=1.0):
+    """oracle SW for two amino-acid strings -> (score, q_end, t_end, q_start, t_start, rev_mismatch); bias_scale: the scale of the
+    composition bias (0 = --comp-bias-corr 0)"""
     global _ALN
     if _ALN is None:
         _ALN = submat(0, 2.0, 0.0)
@@ -67,7 +86,7 @@ def sw(q, t, lanes_byte=32, lanes_word=16, gap_open=11, gap_extend=1, with_start
     cb = np.zeros(max(1, len(q)), dtype=np.int8)
     bias = C.c_int()
     L = lib()
-    L.mko_sw_query_init(C.byref(_ALN), qc.ctypes.data_as(C.c_void_p), C.c_int(len(q)), C.c_float(1.0), cb.ctypes.data_as(C.c_void_p), C.byref(bias))
+    L.mko_sw_query_init(C.byref(_ALN), qc.ctypes.data_as(C.c_void_p), C.c_int(len(q)), C.c_float(bias_scale), cb.ctypes.data_as(C.c_void_p), C.byref(bias))
     r = SwResult()
     L.mko_sw_forward(C.byref(_ALN), qc.ctypes.data_as(C.c_void_p), cb.ctypes.data_as(C.c_void_p), bias, C.c_int(len(q)),
                      tc.ctypes.data_as(C.c_void_p), C.c_int(len(t)), C.c_int(gap_open), C.c_int(gap_extend), C.c_int(lanes_byte), C.c_int(lanes_word), C.byref(r))
@@ -94,6 +113,27 @@ def profile_arrays(entry, n_cols):
     query = np.ctypeslib.as_array(pr.query, shape=(n_cols,)).copy()
     L.mko_profile_free(p)
     return scores, idx, aln, query
+
+
+def sw_profile(entry, n_cols, targets, lanes_byte=32, lanes_word=16, gap_open=11, gap_extend=1):
+    """oracle SW of one profile query (a profile DB entry of n_cols columns) against amino-acid strings: mko_sw_forward_profile and, for a
+    positive score, mko_sw_reverse_profile -> [(score, q_end, t_end, q_start, t_start, rev_mismatch), ...]"""
+    L = lib()
+    L.mko_profile_map.restype = C.POINTER(Profile)
+    p = L.mko_profile_map(C.c_char_p(entry), C.c_int(n_cols))
+    bias = C.c_int(L.mko_sw_profile_bias(p))
+    out = []
+    for t in targets:
+        tc = encode(t)
+        r = SwResult()
+        L.mko_sw_forward_profile(p, bias, tc.ctypes.data_as(C.c_void_p), C.c_int(len(t)), C.c_int(gap_open), C.c_int(gap_extend),
+                                 C.c_int(lanes_byte), C.c_int(lanes_word), C.byref(r))
+        if r.score > 0:
+            L.mko_sw_reverse_profile(p, bias, tc.ctypes.data_as(C.c_void_p), C.c_int(gap_open), C.c_int(gap_extend),
+                                     C.c_int(lanes_byte), C.c_int(lanes_word), C.byref(r))
+        out.append((r.score, r.q_end, r.t_end, r.q_start, r.t_start, r.rev_mismatch))
+    L.mko_profile_free(p)
+    return out
 
 
 def run_pipeline(targets, queries, outdir, extra=()):
