@@ -276,8 +276,8 @@ int mk_align_limit_scan(const uint8_t *verdicts, const uint64_t *offsets, uint32
 int mk_align_backtrace(const mk_queries *q, const char **ops, const uint64_t **ops_offsets /* n_alignments + 1 */, const uint32_t **identities);
 
 /* ---- producer of the query batch: `extractorfs` + `translatenucs` (+ `reverseseq`) as predictexons runs
- * them (util/extractorfs.cpp:19-159, Orf::findAll with orf-start-mode 1, contig start mode 2, genetic code 1; the frames, the gap and
- * length limits, the contig end mode and the null mode are mk_orf_params).  Contigs are ASCII nucleotides (IUPAC codes, lower case,
+ * them (util/extractorfs.cpp:19-159, Orf::findAll, translatenucs.cpp:57-102; the genetic code, the start modes, the frames, the gap and
+ * length limits, the contig start and end modes, the added stop marks and the null mode are mk_orf_params).  Contigs are ASCII nucleotides (IUPAC codes, lower case,
  * U allowed), concatenated, offsets[n_contigs + 1].  Fragment k is what the reference's renumbered ORF DB holds under key k: the order
  * is contig, plus strand then minus strand, end position ascending, whatever the parameters drop. */
 typedef struct mk_orfs mk_orfs;
@@ -297,10 +297,24 @@ typedef struct {               /* the extractorfs flags (Parameters.cpp:2525-255
     int contig_end_mode;       /* --contig-end-mode  0: only fragments without a closing stop, 1: only those with one, 2: both; else MK_ERR_ARG */
     int reverse_fragments;     /* --reverse-fragments 0 / 1 (else MK_ERR_ARG): every protein back to front, records and headers unchanged */
     int pad_;
+    int translation_table;     /* --translation-table 1; one of the genetic codes 1-6, 9-16, 21-31 (TranslateNucl::GenCode), else MK_ERR_ARG: the stop
+                                                     codons of the scan, the start codons of --use-all-table-starts and the residues all follow it */
+    int orf_start_mode;        /* --orf-start-mode   1; 0: from the first start codon after a stop to the next stop, 1: from the codon after a stop,
+                                                     2: from the last start codon before the stop; in every mode a frame begins inside a fragment
+                                                     (incomplete start); else MK_ERR_ARG */
+    int use_all_table_starts;  /* --use-all-table-starts 0: ATG is the only start codon, 1: all start codons of the genetic code; no effect in
+                                                     start mode 1; else MK_ERR_ARG */
+    int contig_start_mode;     /* --contig-start-mode 2; 0: only fragments with an incomplete start, 1: only those with a complete one, 2: both;
+                                                     below 2 with orf_start_mode 1 MK_ERR_ARG (the reference exits there) */
+    int add_orf_stop;          /* --add-orf-stop     0 / 1 (else MK_ERR_ARG): translatenucs' stars -- a '*' before a fragment with a complete start
+                                                     and behind one with a complete end, unless its last codon already translates to '*'; they
+                                                     are residues of the protein (and of the query batch, as X), mirrored with it by
+                                                     reverse_fragments; headers and coordinates do not change.  With it max_codons above
+                                                     65533 is MK_ERR_UNSUPPORTED */
 } mk_orf_params;
 void mk_default_orf_params(mk_orf_params *p);
 int mk_extract_orfs_ex(const char *nucleotides, const uint64_t *offsets, uint32_t n_contigs, const mk_orf_params *params, mk_orfs **out);
-/* = mk_extract_orfs_ex with the defaults and this min_codons */
+/* = mk_extract_orfs_ex with the defaults (genetic code 1, orf start mode 1, contig start mode 2, no added stops) and this min_codons */
 int mk_extract_orfs(const char *nucleotides, const uint64_t *offsets, uint32_t n_contigs, int min_codons, mk_orfs **out);
 /* the same fragments computed on the host, over the same restatement of the rule as the kernels (csrc/mk_orf_scan.hpp): no GPU call, no
  * mk_init needed.  The handle works with every mk_orfs_* call; mk_queries_from_orfs uploads its residue codes. */
@@ -334,7 +348,9 @@ typedef struct {               /* PotentialExon as printed by exonToBuffer (Pred
 } mk_exon;
 typedef struct mk_predictions mk_predictions;
 void mk_default_exon_params(mk_exon_params *p);
-/* q = the batch made by mk_queries_from_orfs(orfs) after mk_search / mk_align.  target_keys (may be NULL: key = index) gives the
+/* q = the batch made by mk_queries_from_orfs(orfs) after mk_search / mk_align.  An ORF set made with add_orf_stop = 1 is MK_ERR_ARG: exon
+ * coordinates are fragment start + 3 * query position, and an added leading '*' shifts the query positions (the reference has no such
+ * path either: its predictexons does not take --add-orf-stop).  mk_predict_exons_arrays cannot know: hand it alignments of unstarred fragments.  target_keys (may be NULL: key = index) gives the
  * DB key of every target: the reference orders a contig's predictions by target KEY and prints it. */
 int mk_predict_exons(const mk_targetdb *db, const mk_orfs *orfs, const mk_queries *q, const mk_exon_params *params,
                      const uint32_t *target_keys, mk_predictions **out);

@@ -406,9 +406,11 @@ ORF_DTYPE = np.dtype([("contig", "<u4"), ("from", "<u4"), ("to", "<u4"), ("incom
 
 
 class OrfParams(C.Structure):
-    """mk_orf_params: the extractorfs flags + --reverse-fragments (include/metaeuk_amd.h)"""
+    """mk_orf_params: the extractorfs flags, translatenucs' --add-orf-stop and --reverse-fragments (include/metaeuk_amd.h)"""
     _fields_ = [("min_codons", C.c_int), ("max_codons", C.c_int), ("max_gap_codons", C.c_int), ("forward_frames", C.c_int),
-                ("reverse_frames", C.c_int), ("contig_end_mode", C.c_int), ("reverse_fragments", C.c_int), ("pad_", C.c_int)]
+                ("reverse_frames", C.c_int), ("contig_end_mode", C.c_int), ("reverse_fragments", C.c_int), ("pad_", C.c_int),
+                ("translation_table", C.c_int), ("orf_start_mode", C.c_int), ("use_all_table_starts", C.c_int),
+                ("contig_start_mode", C.c_int), ("add_orf_stop", C.c_int)]
 
 
 def default_orf_params(**kw):

@@ -1193,6 +1193,7 @@ struct mk_orfs {
     std::vector<char> aa;
     std::vector<uint8_t> codes;
     uint32_t nContigs = 0;
+    bool stars = false;                       // made with add_orf_stop: residue positions are no codon positions (mk_predict_exons refuses)
     ~mk_orfs() { dev.release(); }
 };
 
@@ -1200,10 +1201,12 @@ void mk_default_orf_params(mk_orf_params *p) {
     if (!p) return;
     p->min_codons = 15; p->max_codons = 32734; p->max_gap_codons = INT_MAX;        // Parameters.cpp: orfMinLength, orfMaxLength, orfMaxGaps
     p->forward_frames = 7; p->reverse_frames = 7; p->contig_end_mode = 2; p->reverse_fragments = 0; p->pad_ = 0;
+    p->translation_table = 1; p->orf_start_mode = 1; p->use_all_table_starts = 0; p->contig_start_mode = 2; p->add_orf_stop = 0;
 }
 
 // the checks the device call and the host twin share: arguments, then the rule of mk_orf_scan.hpp
-static int orf_rule_of(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, const mk_orf_params *P, mk_orfs **out, mk::OrfRule &rule) {
+static int orf_rule_of(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, const mk_orf_params *P, mk_orfs **out, mk::OrfRule &rule,
+                       char table[4096]) {
     if (!offsets || !out || !P || (!nucleotides && offsets[nContigs] > 0)) return fail(MK_ERR_ARG, "bad argument");
     if (P->min_codons < 1) return fail(MK_ERR_ARG, "min_codons %d: at least 1", P->min_codons);
     if (P->max_codons < 1) return fail(MK_ERR_ARG, "max_codons %d: at least 1", P->max_codons);
@@ -1212,7 +1215,18 @@ static int orf_rule_of(const char *nucleotides, const uint64_t *offsets, uint32_
         return fail(MK_ERR_ARG, "frame masks %d / %d: three bits, frame f = bit f - 1", P->forward_frames, P->reverse_frames);
     if (P->contig_end_mode < 0 || P->contig_end_mode > 2) return fail(MK_ERR_ARG, "contig_end_mode %d: 0, 1 or 2", P->contig_end_mode);
     if (P->reverse_fragments != 0 && P->reverse_fragments != 1) return fail(MK_ERR_ARG, "reverse_fragments %d: 0 or 1", P->reverse_fragments);
+    if (P->orf_start_mode < 0 || P->orf_start_mode > 2) return fail(MK_ERR_ARG, "orf_start_mode %d: 0, 1 or 2", P->orf_start_mode);
+    if (P->contig_start_mode < 0 || P->contig_start_mode > 2) return fail(MK_ERR_ARG, "contig_start_mode %d: 0, 1 or 2", P->contig_start_mode);
+    if (P->orf_start_mode == 1 && P->contig_start_mode < 2)                    // the reference exits there (extractorfs.cpp:38-41)
+        return fail(MK_ERR_ARG, "orf_start_mode 1 can only go with contig_start_mode 2, got %d", P->contig_start_mode);
+    if (P->use_all_table_starts != 0 && P->use_all_table_starts != 1) return fail(MK_ERR_ARG, "use_all_table_starts %d: 0 or 1", P->use_all_table_starts);
+    if (P->add_orf_stop != 0 && P->add_orf_stop != 1) return fail(MK_ERR_ARG, "add_orf_stop %d: 0 or 1", P->add_orf_stop);
+    uint64_t stopMask = 0, startMask = 0;
+    if (!mk::orf_code_masks(P->translation_table, P->use_all_table_starts != 0, stopMask, startMask) || !mk::build_translation_table(table, P->translation_table))
+        return fail(MK_ERR_ARG, "translation_table %d: one of the genetic codes 1-6, 9-16, 21-31", P->translation_table);
     if (P->max_codons > 65535) return fail(MK_ERR_UNSUPPORTED, "max_codons %d: at most 65535 codons per fragment (--max-length)", P->max_codons);
+    if (P->add_orf_stop && P->max_codons > 65533)
+        return fail(MK_ERR_UNSUPPORTED, "max_codons %d with add_orf_stop: at most 65533 codons per fragment (its residues, two stars included, are kept in 16 bits)", P->max_codons);
     for (uint32_t i = 0; i < nContigs; i++) {
         if (offsets[i + 1] < offsets[i]) return fail(MK_ERR_ARG, "offsets are not ascending at contig %u", i);
         if (offsets[i + 1] - offsets[i] >= 0x7FFFFFF0ull) return fail(MK_ERR_UNSUPPORTED, "contig %u is >= 2^31 nucleotides", i);
@@ -1220,6 +1234,10 @@ static int orf_rule_of(const char *nucleotides, const uint64_t *offsets, uint32_
     rule.min_length = (uint32_t) P->min_codons; rule.max_length = (uint32_t) P->max_codons; rule.max_gaps = (uint32_t) P->max_gap_codons;
     rule.forward_frames = (uint32_t) P->forward_frames; rule.reverse_frames = (uint32_t) P->reverse_frames;
     rule.end_mode = (uint32_t) P->contig_end_mode; rule.reverse = (uint32_t) P->reverse_fragments;
+    rule.start_mode = (uint32_t) P->orf_start_mode; rule.contig_start_mode = (uint32_t) P->contig_start_mode; rule.add_stop = (uint32_t) P->add_orf_stop;
+    rule.stop_mask = stopMask; rule.start_mask = startMask;
+    // the default rule (genetic code 1, any to stop, no stars) keeps the kernels and the host walk it always had
+    rule.general = (P->translation_table != 1 || P->orf_start_mode != 1 || P->add_orf_stop) ? 1u : 0u;
     return MK_OK;
 }
 
@@ -1231,7 +1249,7 @@ static void orf_headers(const std::vector<mk::OrfRecord> &rec, const uint64_t *o
     for (uint64_t k = 0; k < nf; k++) {
         const mk::OrfRecord &r = rec[k];
         const uint32_t len = (uint32_t) (offsets[r.contig + 1] - offsets[r.contig]);
-        const uint32_t sTo = r.s_from + 3 * r.n_aa - 1;           // strand coordinates; the minus strand is mirrored (extractorfs.cpp:88-93)
+        const uint32_t sTo = r.s_from + 3 * r.n_codons - 1;           // strand coordinates; the minus strand is mirrored (extractorfs.cpp:88-93)
         mk_orf &h = orfs[k];
         h.contig = r.contig;
         h.minus_strand = (r.flags & 4u) ? 1 : 0;
@@ -1247,7 +1265,8 @@ int mk_extract_orfs_ex(const char *nucleotides, const uint64_t *offsets, uint32_
     int rc = ensure_ready(false);
     if (rc) return rc;
     mk::OrfRule rule;
-    if ((rc = orf_rule_of(nucleotides, offsets, nContigs, P, out, rule)) != MK_OK) return rc;
+    char table[4096];
+    if ((rc = orf_rule_of(nucleotides, offsets, nContigs, P, out, rule, table)) != MK_OK) return rc;
     HostTimer ht("host_extract_orfs_total");
     hipStream_t up = g_uploadStream ? g_uploadStream : g_stream;
     struct Restore {
@@ -1257,7 +1276,7 @@ int mk_extract_orfs_ex(const char *nucleotides, const uint64_t *offsets, uint32_
     t_stream = up;
     mk::set_scratch_lane(UPLOAD_LANE);
     mk_orfs *o = new mk_orfs();
-    o->nContigs = nContigs;
+    o->nContigs = nContigs; o->stars = rule.add_stop != 0;
     DevBuf<char> dNucl;
     DevBuf<uint64_t> dOff;
     dNucl.pooled = true; dOff.pooled = true;
@@ -1267,7 +1286,7 @@ int mk_extract_orfs_ex(const char *nucleotides, const uint64_t *offsets, uint32_
     if (e != hipSuccess) { delete o; return fail(MK_ERR_DEVICE, "contig upload failed: %s", hipGetErrorString(e)); }
     std::string err;
     const int th = timed_begin("extract_orfs", (double) offsets[nContigs] * 2.0, 0);
-    rc = mk::run_extract_orfs(dNucl.p, dOff.p, nContigs, rule, up, o->dev, err);
+    rc = mk::run_extract_orfs(dNucl.p, dOff.p, nContigs, rule, table, up, o->dev, err);
     timed_end(th);
     timed_flush();
     if (rc != MK_OK) { delete o; return fail(rc, "%s", err.c_str()); }
@@ -1296,11 +1315,12 @@ int mk_extract_orfs(const char *nucleotides, const uint64_t *offsets, uint32_t n
 
 int mk_extract_orfs_host(const char *nucleotides, const uint64_t *offsets, uint32_t nContigs, const mk_orf_params *P, mk_orfs **out) {
     mk::OrfRule rule;
-    if (int rc = orf_rule_of(nucleotides, offsets, nContigs, P, out, rule)) return rc;
+    char table[4096];
+    if (int rc = orf_rule_of(nucleotides, offsets, nContigs, P, out, rule, table)) return rc;
     mk::OrfHostResult H;
-    mk::extract_orfs_host(nucleotides, offsets, nContigs, rule, H);
+    mk::extract_orfs_host(nucleotides, offsets, nContigs, rule, table, H);
     mk_orfs *o = new mk_orfs();
-    o->nContigs = nContigs;
+    o->nContigs = nContigs; o->stars = rule.add_stop != 0;
     orf_headers(H.records, offsets, o->orfs);
     o->aaOff.swap(H.aa_off); o->aa.swap(H.aa); o->codes.swap(H.codes);
     *out = o;
@@ -1338,6 +1358,8 @@ int mk_predict_exons(const mk_targetdb *db, const mk_orfs *orfs, const mk_querie
     if (!db || !orfs || !q || !P || !out) return fail(MK_ERR_ARG, "null argument");
     if (!q->haveAln) return fail(MK_ERR_ARG, "no alignment result in this batch: run mk_search or mk_align first");
     if (q->n != orfs->orfs.size()) return fail(MK_ERR_ARG, "the batch has %u queries, the ORF set %zu fragments", q->n, orfs->orfs.size());
+    // a leading '*' shifts every query position of a fragment by one residue, and the exon coordinates are orf.from + 3 * query position
+    if (orfs->stars) return fail(MK_ERR_ARG, "the ORF set was made with add_orf_stop: its residues are no codon positions, exon sets need fragments without the added stops");
     HostTimer ht("host_predict_exons_total");
     mk_predictions *p = new mk_predictions();
     mk::predict_exons(orfs->orfs.data(), orfs->orfs.size(), orfs->nContigs, (const mk_alignment *) q->alns.p, q->alnOff.data(), targetKeys, mk_targetdb_residues(db), *P,

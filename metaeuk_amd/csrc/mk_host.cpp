@@ -547,10 +547,67 @@ void build_orf_tables(char comp[256], uint8_t base[256]) {
     for (int i = 0; i < 16; i++) base[i] = static_cast<uint8_t>(i);
 }
 
-// TranslateNucl::initTranslationTable (TranslateNucl.h:344-483) for the canonical code: the residue common to all the
-// unambiguous codons an IUPAC codon stands for, with the B (D/N), Z (E/Q), J (I/L) unions, else X
-void build_translation_table(char table[4096]) {
-    const char *aaOf = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";   // TCAG order
+// The genetic codes of --translation-table: residues and start marks of the 64 codons in TCAG order, in the layout of NCBI's gc.prt, for the
+// 25 codes of TranslateNucl::GenCode.  The VALUES are those the reference binary translates and scans with, because results have to equal
+// its results bit for bit; where it differs from gc.prt the binary wins: codes 27-30 read CTG as A here (gc.prt: L).  Pinned to the
+// binary: all 4096 table entries of every code (tests/golden/orf_code_tables) and the start set of every code (orf_code_starts).
+namespace {
+struct GeneticCode { int id; const char *aa; const char *starts; };
+const GeneticCode kGeneticCodes[] = {
+    { 1, "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "---M------**--*----M---------------M----------------------------"},
+    { 2, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSS**VVVVAAAADDEEGGGG", "----------**--------------------MMMM----------**---M------------"},
+    { 3, "FFLLSSSSYY**CCWWTTTTPPPPHHQQRRRRIIMMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------**----------------------MM----------------------------"},
+    { 4, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "--MM------**-------M------------MMMM---------------M------------"},
+    { 5, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSSSVVVVAAAADDEEGGGG", "---M------**--------------------MMMM---------------M------------"},
+    { 6, "FFLLSSSSYYQQCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "--------------*--------------------M----------------------------"},
+    { 9, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG", "----------**-----------------------M---------------M------------"},
+    {10, "FFLLSSSSYY**CCCWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------**-----------------------M----------------------------"},
+    {11, "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "---M------**--*----M------------MMMM---------------M------------"},
+    {12, "FFLLSSSSYY**CC*WLLLSPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------**--*----M---------------M----------------------------"},
+    {13, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSGGVVVVAAAADDEEGGGG", "---M------**----------------------MM---------------M------------"},
+    {14, "FFLLSSSSYYY*CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG", "-----------*-----------------------M----------------------------"},
+    {15, "FFLLSSSSYY*QCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------*---*--------------------M----------------------------"},
+    {16, "FFLLSSSSYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------*---*--------------------M----------------------------"},
+    {21, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNNKSSSSVVVVAAAADDEEGGGG", "----------**-----------------------M---------------M------------"},
+    {22, "FFLLSS*SYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "------*---*---*--------------------M----------------------------"},
+    {23, "FF*LSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "--*-------**--*-----------------M--M---------------M------------"},
+    {24, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSSKVVVVAAAADDEEGGGG", "---M------**-------M---------------M---------------M------------"},
+    {25, "FFLLSSSSYY**CCGWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "---M------**-----------------------M---------------M------------"},
+    {26, "FFLLSSSSYY**CC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------**--*----M---------------M----------------------------"},
+    {27, "FFLLSSSSYYQQCCWWLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "--------------*--------------------M----------------------------"},
+    {28, "FFLLSSSSYYQQCCWWLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------**--*--------------------M----------------------------"},
+    {29, "FFLLSSSSYYYYCC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "--------------*--------------------M----------------------------"},
+    {30, "FFLLSSSSYYEECC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "--------------*--------------------M----------------------------"},
+    {31, "FFLLSSSSYYEECCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", "----------**-----------------------M----------------------------"},
+};
+const GeneticCode *genetic_code(int id) {
+    for (const GeneticCode &g : kGeneticCodes) if (g.id == id) return &g;
+    return nullptr;
+}
+}  // namespace
+
+// TranslateNucl::getStopCodons / getStartCodons (TranslateNucl.h:279-315, 434-463): every '*' of the residue string, every 'M' of the start
+// string (its '*' marks are not starts), as sets in the A C G T order of the scan
+bool orf_code_masks(int geneticCode, bool allStarts, uint64_t &stopMask, uint64_t &startMask) {
+    const GeneticCode *g = genetic_code(geneticCode);
+    if (!g) return false;
+    static const int acgtOfTcag[4] = {3, 1, 0, 2};
+    stopMask = 0; startMask = 0;
+    for (int cd = 0; cd < 64; cd++) {
+        const int idx = 16 * acgtOfTcag[cd >> 4] + 4 * acgtOfTcag[(cd >> 2) & 3] + acgtOfTcag[cd & 3];
+        if (g->aa[cd] == '*') stopMask |= 1ull << idx;
+        if (g->starts[cd] == 'M') startMask |= 1ull << idx;
+    }
+    if (!allStarts) startMask = 1ull << (16 * 0 + 4 * 3 + 2);                      // ATG (Orf.cpp:73-78)
+    return true;
+}
+
+// TranslateNucl::initTranslationTable (TranslateNucl.h:344-483): the residue common to all the unambiguous codons an IUPAC codon
+// stands for, with the B (D/N), Z (E/Q), J (I/L) unions, else X
+bool build_translation_table(char table[4096], int geneticCode) {
+    const GeneticCode *g = genetic_code(geneticCode);
+    if (!g) return false;
+    const char *aaOf = g->aa;                                                     // TCAG order
     auto tcag = [](int bit) { return bit == 8 ? 0 : bit == 2 ? 1 : bit == 1 ? 2 : 3; };
     for (int i = 0; i < 16; i++)
         for (int j = 0; j < 16; j++)
@@ -576,6 +633,7 @@ void build_translation_table(char table[4096]) {
                 }
                 table[256 * i + 16 * j + k] = aa ? aa : 'X';
             }
+    return true;
 }
 
 size_t format_orf_header(char *buf, uint32_t key, uint32_t from, uint32_t to, bool incompleteStart, bool incompleteEnd) {

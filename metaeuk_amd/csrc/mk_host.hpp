@@ -91,8 +91,12 @@ int select_hits(std::vector<Cand> &cands, int binCount, int maxHits, int minDiag
 // ---- extractorfs --translate (Orf.cpp, TranslateNucl.h) ----
 // comp[c] = Orf::iupacReverseComplementTable ('.' = not a nucleotide code); base[c] = TranslateNucl::sm_BaseToIdx (4-bit IUPAC sets)
 void build_orf_tables(char comp[256], uint8_t base[256]);
-// residue of every base-code triple (256 i + 16 j + k) under genetic code 1, ambiguity resolved like TranslateNucl::initTranslationTable
-void build_translation_table(char table[4096]);
+// residue of every base-code triple (256 i + 16 j + k) under one of the 25 genetic codes of TranslateNucl::GenCode (1-6, 9-16, 21-31),
+// ambiguity resolved like TranslateNucl::initTranslationTable; false for any other number
+bool build_translation_table(char table[4096], int geneticCode = 1);
+// the stop codons and the start codons (allStarts: all of the code's, else ATG alone) of a genetic code as sets over the 64 plain
+// codons, bit 16 a + 4 b + c with A = 0, C = 1, G = 2, T = 3 (mk_orf_scan.hpp: OrfRule::stop_mask / start_mask); false for an unknown code
+bool orf_code_masks(int geneticCode, bool allStarts, uint64_t &stopMask, uint64_t &startMask);
 // Orf::writeOrfHeader without the newline: "key<TAB>from(+|-)len[<TAB>complete]"
 size_t format_orf_header(char *buf, uint32_t key, uint32_t from, uint32_t to, bool incompleteStart, bool incompleteEnd);
 

@@ -1,14 +1,17 @@
 // metaeuk_amd/csrc/mk_orf.hip -- six-frame ORF fragments of a batch of contigs, translated, on the GPU
-// (the producer of the hot path's queries).  Replaces, for orf-start-mode 1, contig start mode 2 and
-// genetic code 1, with the frame masks, --max-gaps, --min-length / --max-length, --contig-end-mode and --reverse-fragments of the caller:
-//   Orf::setSequence / findAll / findForward    M/src/commons/Orf.cpp:118-345
+// (the producer of the hot path's queries).  Replaces, for every genetic code (--translation-table),
+// --orf-start-mode, --contig-start-mode and --add-orf-stop, with the frame masks, --max-gaps, --min-length / --max-length,
+// --contig-end-mode and --reverse-fragments of the caller:
+//   Orf::Orf / setSequence / findAll / findForward    M/src/commons/Orf.cpp:55-96, 118-345
+//   translatenucs' --add-orf-stop               M/src/util/translatenucs.cpp:57-102
 //   the extractorfs loop, --translate branch    M/src/util/extractorfs.cpp:64-125
 //   TranslateNucl::translate                    M/src/commons/TranslateNucl.h:488-503 (IUPAC-aware table: mk_host.cpp)
 //   reverseseq                                  M/src/util/reverseseq.cpp:41-47
 // The rule itself (Strand, stop_at, fragment_at, translate_at) is mk_orf_scan.hpp, shared with the host twin of mk_orf_host.cpp.
 // Layout: contigs stay as the caller's ASCII in HBM; nothing is copied or reverse-complemented -- the minus strand is an
 // index transform + complement lookup.  Three kernels:
-//   orf_mark_kernel          one lane per strand position: does a fragment end here, and how many codons has it
+//   orf_mark_kernel          one lane per strand position: does a fragment end here, and how many codons has it (the default rule: code 1,
+//                            start mode 1, no stars; orf_mark_modes_kernel<MODE> / orf_write_modes_kernel<MODE> for every other rule)
 //   orf_scan_*_kernel        two prefix sums in one pass (fragments, residues): the rank of every fragment = the reference's output order
 //                            (= the renumbered ORF ids) and its residue offset
 //   orf_write_kernel         one record per fragment at its rank
@@ -75,7 +78,44 @@ __global__ __launch_bounds__(256) void orf_write_kernel(OrfScanArgs A, uint64_t 
     locate(A, x, contig, S, p);
     const uint32_t n = fragment_at<GAPS>(S, p, A.rule, from, flags);
     OrfRecord r;
-    r.contig = contig; r.s_from = from; r.n_aa = n; r.flags = flags;
+    r.contig = contig; r.s_from = from; r.n_codons = n; r.flags = flags;
+    A.records[rank[x]] = r;
+    A.aa_off[rank[x]] = aaBase[x];
+}
+
+// The same two kernels for every other rule (A.rule.general: another genetic code, start mode 0 or 2, --add-orf-stop): fragment_at_modes of
+// mk_orf_scan.hpp.  MODE is the start mode; the stop and start sets are two 64-bit masks of the kernel arguments and `table` is one pointer,
+// all launch-uniform.  table != nullptr only with --add-orf-stop: the closing lane then translates the fragment's last codon (one load) to
+// know whether a '*' follows it, and naa[] holds RESIDUES (codons + stars, <= 65535 by the caller's check).
+template <int MODE>
+__global__ __launch_bounds__(256) void orf_mark_modes_kernel(OrfScanArgs A, uint64_t nPos, const char *table, uint16_t *naa) {
+    const uint64_t x = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= nPos) return;
+    uint32_t contig, p, from = 0, flags = 0;
+    Strand S;
+    uint32_t n = 0;
+    if (locate(A, x, contig, S, p)) {
+        n = fragment_at_modes<MODE>(S, p, A.rule, from, flags);
+        if (n && table) n += orf_star_count(orf_star_flags(S, from, n, flags, table));
+    }
+    naa[x] = (uint16_t) n;
+}
+
+// (the stars need no second translation: naa[] has the residues, the walk gives the codons, and the leading star follows from the flags)
+template <int MODE>
+__global__ __launch_bounds__(256) void orf_write_modes_kernel(OrfScanArgs A, uint64_t nPos, const uint16_t *naa, const uint64_t *rank, const uint64_t *aaBase) {
+    const uint64_t x = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= nPos || naa[x] == 0) return;
+    uint32_t contig, p, from = 0, flags = 0;
+    Strand S;
+    locate(A, x, contig, S, p);
+    const uint32_t n = fragment_at_modes<MODE>(S, p, A.rule, from, flags);
+    if (A.rule.add_stop) {
+        const uint32_t lead = (flags & 1u) ? 0u : 1u, stars = (uint32_t) naa[x] - n;
+        flags |= (lead ? 8u : 0u) | (stars > lead ? 16u : 0u);
+    }
+    OrfRecord r;
+    r.contig = contig; r.s_from = from; r.n_codons = n; r.flags = flags;
     A.records[rank[x]] = r;
     A.aa_off[rank[x]] = aaBase[x];
 }
@@ -137,6 +177,8 @@ __global__ __launch_bounds__(256) void orf_scan_apply_kernel(const uint16_t *naa
     if (blockIdx.x == 0 && threadIdx.x == 0) { rank[n] = blockSums[2 * (size_t) blocks]; aaBase[n] = blockSums[2 * (size_t) blocks + 1]; }
 }
 
+// STARS: the launch has --add-orf-stop; residue i of a fragment is then codon i - (leading star), and the stars are residues of their own
+template <bool STARS>
 __global__ __launch_bounds__(256) void orf_translate_kernel(OrfScanArgs A, uint64_t nFrag, uint64_t nAa, const char *table /* [4096] */,
                                                             char *aaAscii, uint8_t *aaCode) {
     __shared__ char sTable[4096];
@@ -150,8 +192,12 @@ __global__ __launch_bounds__(256) void orf_translate_kernel(OrfScanArgs A, uint6
     Strand S;
     S.seq = A.nucl + A.offsets[r.contig]; S.len = (uint32_t) (A.offsets[r.contig + 1] - A.offsets[r.contig]); S.minus = (r.flags & 4u) != 0;
     const uint32_t i = (uint32_t) (x - A.aa_off[lo]);
-    const char aa = translate_at(S, r.s_from + 3u * i, sTable);
-    const uint64_t w = A.aa_off[lo] + orf_residue_slot(i, r.n_aa, A.rule.reverse);      // --reverse-fragments: the mirrored slot of the same fragment
+    const uint32_t lead = STARS ? (r.flags >> 3) & 1u : 0u;
+    const uint32_t nRes = STARS ? r.n_codons + orf_star_count(r.flags) : r.n_codons;
+    char aa;
+    if (STARS && (i < lead || i - lead >= r.n_codons)) aa = '*';
+    else aa = translate_at(S, r.s_from + 3u * (i - lead), sTable);
+    const uint64_t w = A.aa_off[lo] + orf_residue_slot(i, nRes, A.rule.reverse);        // --reverse-fragments: the mirrored slot of the same fragment, stars included
     aaAscii[w] = aa;
     aaCode[w] = cAaCode[(unsigned char) aa];
 }
@@ -163,8 +209,8 @@ bool g_tablesReady = false;
 #define OCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return MK_ERR_DEVICE; } } while (0)
 #define ONULL(p) do { if (!(p)) { err = "device scratch allocation failed (" #p ")"; return MK_ERR_DEVICE; } } while (0)
 
-int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, const OrfRule &rule, hipStream_t stream, OrfDeviceResult &R,
-                     std::string &err) {
+int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, const OrfRule &rule, const char *table, hipStream_t stream,
+                     OrfDeviceResult &R, std::string &err) {
     if (!g_tablesReady) {
         char comp[256]; uint8_t base[256], code[256];
         build_orf_tables(comp, base);
@@ -190,19 +236,22 @@ int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nCont
     uint64_t *dAaBase = (uint64_t *) dev_scratch("orf_aabase", (nPos + 1) * 8);
     char *dTable = (char *) dev_scratch("orf_table", 4096);
     ONULL(dNaa); ONULL(dRank); ONULL(dAaBase); ONULL(dTable);
-    {
-        char table[4096];
-        build_translation_table(table);
-        OCHK(hipMemcpyAsync(dTable, table, 4096, hipMemcpyHostToDevice, stream));
-        OCHK(hipStreamSynchronize(stream));                              // `table` lives on this frame
-    }
+    OCHK(hipMemcpyAsync(dTable, table, 4096, hipMemcpyHostToDevice, stream));
+    OCHK(hipStreamSynchronize(stream));                                  // `table` is the caller's
     OrfScanArgs A;
     A.nucl = dNucl; A.offsets = dOffsets; A.n_contigs = nContigs;
     A.rule = rule;
     const bool gaps = orf_rule_counts_gaps(rule);                        // launch-uniform: which instance of the two walking kernels runs
     A.records = nullptr; A.aa_off = nullptr;
     const unsigned blocks = (unsigned) ((nPos + 255) / 256);
-    if (gaps) hipLaunchKernelGGL(orf_mark_kernel<true>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa);
+    // the default rule keeps its two instances; every other one runs the instance of its start mode (the mark kernel gets the table only
+    // when it has stars to decide)
+    const char *dStarTable = rule.add_stop ? dTable : nullptr;
+    if (rule.general) {
+        if (rule.start_mode == 0) hipLaunchKernelGGL(orf_mark_modes_kernel<0>, dim3(blocks), dim3(256), 0, stream, A, nPos, dStarTable, dNaa);
+        else if (rule.start_mode == 1) hipLaunchKernelGGL(orf_mark_modes_kernel<1>, dim3(blocks), dim3(256), 0, stream, A, nPos, dStarTable, dNaa);
+        else hipLaunchKernelGGL(orf_mark_modes_kernel<2>, dim3(blocks), dim3(256), 0, stream, A, nPos, dStarTable, dNaa);
+    } else if (gaps) hipLaunchKernelGGL(orf_mark_kernel<true>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa);
     else hipLaunchKernelGGL(orf_mark_kernel<false>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa);
     OCHK(hipGetLastError());
     {
@@ -228,11 +277,16 @@ int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nCont
     R.aa_code = (uint8_t *) dev_block_alloc(std::max<uint64_t>(nAa, 1), &R.cap[3]);
     ONULL(R.records); ONULL(R.aa_off); ONULL(R.aa_ascii); ONULL(R.aa_code);
     A.records = R.records; A.aa_off = R.aa_off;
-    if (gaps) hipLaunchKernelGGL(orf_write_kernel<true>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
+    if (rule.general) {
+        if (rule.start_mode == 0) hipLaunchKernelGGL(orf_write_modes_kernel<0>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
+        else if (rule.start_mode == 1) hipLaunchKernelGGL(orf_write_modes_kernel<1>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
+        else hipLaunchKernelGGL(orf_write_modes_kernel<2>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
+    } else if (gaps) hipLaunchKernelGGL(orf_write_kernel<true>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
     else hipLaunchKernelGGL(orf_write_kernel<false>, dim3(blocks), dim3(256), 0, stream, A, nPos, dNaa, dRank, dAaBase);
     OCHK(hipGetLastError());
     OCHK(hipMemcpyAsync(R.aa_off + nFrag, dAaBase + nPos, 8, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(orf_translate_kernel, dim3((unsigned) ((nAa + 255) / 256)), dim3(256), 0, stream, A, nFrag, nAa, dTable, R.aa_ascii, R.aa_code);
+    if (rule.add_stop) hipLaunchKernelGGL(orf_translate_kernel<true>, dim3((unsigned) ((nAa + 255) / 256)), dim3(256), 0, stream, A, nFrag, nAa, (const char *) dTable, R.aa_ascii, R.aa_code);
+    else hipLaunchKernelGGL(orf_translate_kernel<false>, dim3((unsigned) ((nAa + 255) / 256)), dim3(256), 0, stream, A, nFrag, nAa, (const char *) dTable, R.aa_ascii, R.aa_code);
     OCHK(hipGetLastError());
     OCHK(hipStreamSynchronize(stream));
     return MK_OK;

@@ -11,8 +11,9 @@
 namespace mk {
 
 // one fragment: position on its strand (s_from = first nucleotide in strand coordinates), length in codons,
-// flags: 1 = incomplete start, 2 = incomplete end (no stop codon), 4 = minus strand
-struct OrfRecord { uint32_t contig; uint32_t s_from; uint32_t n_aa; uint32_t flags; };
+// flags: 1 = incomplete start, 2 = incomplete end (no stop codon), 4 = minus strand, 8 / 16 = --add-orf-stop put a '*' before / behind
+// the translated codons: the fragment has n_codons + orf_star_count(flags) residues, and its header and coordinates know codons only
+struct OrfRecord { uint32_t contig; uint32_t s_from; uint32_t n_codons; uint32_t flags; };
 
 struct OrfScanArgs {
     const char *nucl; const uint64_t *offsets; uint32_t n_contigs;
@@ -29,12 +30,14 @@ struct OrfDeviceResult {
 };
 
 // contigs (ASCII, concatenated, offsets[n+1]) already in HBM -> fragments in the reference's output order
-int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, const OrfRule &rule, hipStream_t stream, OrfDeviceResult &R,
-                     std::string &err);
+// (`table` = mk::build_translation_table of the rule's genetic code)
+int run_extract_orfs(const char *dNucl, const uint64_t *dOffsets, uint32_t nContigs, const OrfRule &rule, const char *table /* [4096] */,
+                     hipStream_t stream, OrfDeviceResult &R, std::string &err);
 
 // the same fragments on the host, no GPU call (mk_orf_host.cpp): the twin the kernels are checked against.  records / aaOff[n + 1] / aa / codes
 // are what the device call downloads.
 struct OrfHostResult { std::vector<OrfRecord> records; std::vector<uint64_t> aa_off; std::vector<char> aa; std::vector<uint8_t> codes; };
-void extract_orfs_host(const char *nucl, const uint64_t *offsets, uint32_t nContigs, const OrfRule &rule, OrfHostResult &out);
+void extract_orfs_host(const char *nucl, const uint64_t *offsets, uint32_t nContigs, const OrfRule &rule, const char *table /* [4096] */,
+                       OrfHostResult &out);
 
 }  // namespace mk
