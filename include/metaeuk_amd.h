@@ -275,6 +275,25 @@ int mk_align_limit_scan(const uint8_t *verdicts, const uint64_t *offsets, uint32
  * Views owned by the batch handle.  MK_ERR_ARG when the batch was not aligned with add_backtrace. */
 int mk_align_backtrace(const mk_queries *q, const char **ops, const uint64_t **ops_offsets /* n_alignments + 1 */, const uint32_t **identities);
 
+/* ---- rescorediagonal: the ungapped alignment of every prefilter hit on its diagonal (M/src/alignment/rescorediagonal.cpp:193-364,
+ * DistanceCalculator.h:93-201), the stage `search --alignment-mode 4` runs in place of align (Search.cpp:261, 314-315, 387).  Reads the batch's
+ * prefilter result (mk_prefilter or mk_prefilter_result_set) and fills its ALIGNMENT result: mk_align_result, mk_format_alignment(_bt) and, with
+ * params->add_backtrace = 1, mk_align_backtrace (aln_len operations M) read it unchanged; raw_score is the ungapped score.  Scores are the alignment
+ * matrix on the unmasked residues, no composition bias; e-values and bit scores are those of the GAPLESS statistics (EvalueComputation.h:70-75,
+ * the two-argument constructor of rescorediagonal.cpp:107), not the gap-open 11 / gap-extend 1 set of mk_align.  Honoured of params: evalue_thr, cov_thr, cov_mode, seq_id_thr, seq_id_mode, min_aln_len,
+ * add_backtrace; alignment_mode is ignored.  rescore_mode: 2 (RESCORE_MODE_ALIGNMENT); 0, 1, 3 and 4 MK_ERR_UNSUPPORTED (0 and 1 write hit lists,
+ * not alignments).  sort_results: 0 = the order of the prefilter list, 1 = Matcher::compareHits.  Works on mk_targetdb_create_sequences
+ * databases.  Profile queries or a profile database: MK_ERR_UNSUPPORTED (the reference refuses them, Search.cpp:262-266).  A hit whose 16-bit
+ * diagonal stands for no real diagonal that crosses the pair's rectangle: MK_ERR_ARG.  An ungapped score of 4096 and more (beyond the e-value
+ * table of the alignment stage): MK_ERR_UNSUPPORTED. */
+int mk_rescore_diagonal(mk_targetdb *db, mk_queries *q, const mk_params *params, int rescore_mode, int sort_results);
+/* the same on one pair, host code without a GPU and without mk_init (the twin the kernel is checked against): mat21x21 = int8 scores [q * 21 + t]
+ * (NULL: the alignment matrix), q / t = residue codes, db_residues = residues of the target database (the e-value).  Fills *out (db_key = 0) and
+ * *identities (may be NULL).  Returns 1 = the record is kept, 0 = dropped (a pair that fails Util::canBeCovered is dropped unscored: *out zeroed),
+ * MK_ERR_ARG / MK_ERR_UNSUPPORTED as mk_rescore_diagonal. */
+int mk_rescore_diagonal_host(const int8_t *mat21x21, const uint8_t *q, int q_len, const uint8_t *t, int t_len, uint16_t diagonal, uint64_t db_residues,
+                             const mk_params *params, int rescore_mode, mk_alignment *out, uint32_t *identities);
+
 /* ---- producer of the query batch: `extractorfs` + `translatenucs` (+ `reverseseq`) as predictexons runs
  * them (util/extractorfs.cpp:19-159, Orf::findAll, translatenucs.cpp:57-102; the genetic code, the start modes, the frames, the gap and
  * length limits, the contig start and end modes, the added stop marks and the null mode are mk_orf_params).  Contigs are ASCII nucleotides (IUPAC codes, lower case,

@@ -54,7 +54,8 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_synth_targets", "mk_synth_fragments", "mk_synth_seqdb", "mk_synth_write_seqdb", "mk_targetdb_create_sequences", "mk_prefilter_statistics",
            "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size",
            "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band",
-           "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host", "mk_align_statistics", "mk_align_limit_scan"]
+           "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host", "mk_align_statistics", "mk_align_limit_scan",
+           "mk_rescore_diagonal", "mk_rescore_diagonal_host"]
 
 
 def lib():
@@ -162,6 +163,17 @@ class TargetDB:
     def from_codes(cls, res, off, params=None):
         """res: uint8 codes 0..20 in matrix alphabet order (ACDEFGHIKLMNPQRSTVWYX), off: uint64[n+1]"""
         return cls(None, params, _codes=(np.ascontiguousarray(res, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint64)))
+
+    @classmethod
+    def sequences(cls, res, off, params=None):
+        """the target side as the alignment stages need it (mk_targetdb_create_sequences): residue codes only, no masking, no k-mer index"""
+        self = cls.__new__(cls)
+        self.params = params or default_params()
+        self.res, self.off = np.ascontiguousarray(res, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint64)
+        self.n = len(self.off) - 1
+        self.h = C.c_void_p()
+        _chk(lib().mk_targetdb_create_sequences(_p(self.res), _p(self.off), C.c_uint32(self.n), C.byref(self.params), C.byref(self.h)))
+        return self
 
     def masked(self):
         out = np.zeros(max(1, int(self.off[-1])), dtype=np.uint8)
@@ -629,6 +641,29 @@ def align_limit_scan(verdicts, offsets, max_accept, max_rejected, state=None):
     _chk(lib().mk_align_limit_scan(_p(vv), _p(off), C.c_uint32(n), C.c_int(int(max_accept)), C.c_int(int(max_rejected)),
                                    None if state is None else _p(state), _p(keep), _p(looked)))
     return keep[:len(v)], looked[:n]
+
+
+# the rescoring kernel's work split: lanes per pair, cells per lane and sweep (csrc/mk_rescore.hpp)
+RESCORE_GROUP, RESCORE_SEG = 8, 8
+
+
+def rescore_diagonal(db, q, params=None, rescore_mode=2, sort_results=0):
+    """rescorediagonal --rescore-mode 2 over the batch's prefilter result -> (ctypes array of Alignment [total], offsets uint64[n+1])"""
+    p = params or db.params
+    _chk(lib().mk_rescore_diagonal(db.h, q.h, C.byref(p), C.c_int(int(rescore_mode)), C.c_int(int(sort_results))))
+    return align_result(q)
+
+
+def rescore_diagonal_host(q, t, diagonal, db_residues, params, mat=None, rescore_mode=2):
+    """the same on one pair of code arrays, host code (mk_rescore_diagonal_host) -> (kept, Alignment, identities)"""
+    q = np.ascontiguousarray(q, dtype=np.uint8); t = np.ascontiguousarray(t, dtype=np.uint8)
+    m = None if mat is None else np.ascontiguousarray(mat, dtype=np.int8)
+    a, ids = Alignment(), C.c_uint32()
+    rc = lib().mk_rescore_diagonal_host(None if m is None else _p(m), _p(q), C.c_int(len(q)), _p(t), C.c_int(len(t)), C.c_uint16(int(diagonal) & 0xFFFF),
+                                        C.c_uint64(int(db_residues)), C.byref(params), C.c_int(int(rescore_mode)), C.byref(a), C.byref(ids))
+    if rc < 0:
+        _chk(rc)
+    return rc == 1, a, int(ids.value)
 
 
 def sw_pairs(db, q, q_idx, t_idx, with_start=True, params=None):

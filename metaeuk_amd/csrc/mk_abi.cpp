@@ -14,6 +14,7 @@
 #include "mk_index.hpp"
 #include "mk_prefilter.hpp"
 #include "mk_profile.hpp"
+#include "mk_rescore.hpp"
 #include "mk_trace.hpp"
 
 #include <algorithm>
@@ -285,6 +286,7 @@ struct mk_targetdb {
     // score tables of the alignment stage, kept from call to call: the e-value row of a query length depends on the database alone, and
     // consecutive batches of ORF fragments bring the same lengths (a batch of other lengths adds its rows; the device copy follows the id)
     std::unordered_map<uint32_t, std::vector<double>> evalueRows;
+    std::unordered_map<uint32_t, std::vector<double>> gaplessRows;    // the same for the ungapped statistics of mk_rescore_diagonal
     std::shared_ptr<const struct ScoreTabs> scoreTabs;     // the newest snapshot (immutable: the batches in flight hold the one they were given)
 };
 
@@ -2057,6 +2059,145 @@ int mk_align(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if (rc != MK_OK) return rc;
     q->haveAln = true;
     if (P->add_backtrace == 1) { if (q->btOff.empty()) q->btOff.push_back(0); q->haveBt = true; }
+    return MK_OK;
+}
+
+// ---- rescorediagonal --rescore-mode 2 (mk_rescore.hpp / mk_rescore.hip) -----------------------------------------------------------
+static int check_rescore(const mk_params *P, int rescoreMode, int sortResults) {
+    if (rescoreMode < 0 || rescoreMode > 4) return fail(MK_ERR_ARG, "--rescore-mode %d out of range (0 to 4)", rescoreMode);
+    if (rescoreMode != mk::RESCORE_MODE_ALIGNMENT)
+        return fail(MK_ERR_UNSUPPORTED, "--rescore-mode %d is not implemented (2: ungapped alignment; 0 and 1 write hit lists, 3 and 4 are other alignments)", rescoreMode);
+    if (sortResults != 0 && sortResults != 1) return fail(MK_ERR_ARG, "--sort-results %d out of range (0 or 1)", sortResults);
+    if (!mk::filter_in_range(mk::result_filter_of(*P)))
+        return fail(MK_ERR_ARG, "result filters out of range: -c %g --cov-mode %d --min-seq-id %g (thresholds in [0, 1], coverage modes 0 to 5)", (double) P->cov_thr, P->cov_mode, (double) P->seq_id_thr);
+    if (P->add_backtrace != 0 && P->add_backtrace != 1) return fail(MK_ERR_ARG, "-a %d out of range (0 or 1)", P->add_backtrace);
+    if (P->seq_id_mode < 0 || P->seq_id_mode > 2) return fail(MK_ERR_ARG, "--seq-id-mode %d out of range (0 to 2)", P->seq_id_mode);
+    return MK_OK;
+}
+
+int mk_rescore_diagonal_host(const int8_t *mat, const uint8_t *q, int qLen, const uint8_t *t, int tLen, uint16_t diagonal, uint64_t dbResidues,
+                             const mk_params *P, int rescoreMode, mk_alignment *out, uint32_t *identities) {
+    if (!q || !t || !P || !out || qLen <= 0 || tLen <= 0) return fail(MK_ERR_ARG, "mk_rescore_diagonal_host: null argument or empty sequence");
+    int rc = check_rescore(P, rescoreMode, 0);
+    if (rc != MK_OK) return rc;
+    std::memset(out, 0, sizeof(*out));
+    if (identities) *identities = 0;
+    const mk::RescoreCriteria C = mk::rescore_criteria_of(*P);
+    if (!mk::can_be_covered(C.filter.cov_thr, C.filter.cov_mode, (float) qLen, (float) tLen)) return 0;     // before the diagonal is looked at, as in the kernel
+    if (!mk::rescore_diagonal_valid(diagonal, (uint32_t) qLen, (uint32_t) tLen))
+        return fail(MK_ERR_ARG, "diagonal %u stands for no real diagonal that crosses a %d x %d rectangle", (unsigned) diagonal, qLen, tLen);
+    int8_t own[441];
+    if (!mat) {
+        mk::SubMat m;
+        mk::build_submat(m, mk::MAT_BLOSUM62, 2.0f, 0.0f);
+        for (int i = 0; i < 21; i++) for (int j = 0; j < 21; j++) own[i * 21 + j] = (int8_t) m.sub[i][j];
+        mat = own;
+    }
+    mk::RescoreBest best;
+    for (uint32_t k = 0; k < mk::rescore_candidates((uint32_t) qLen, (uint32_t) tLen); k++) {
+        const int real = mk::rescore_candidate(k, diagonal, (uint32_t) tLen);
+        const mk::RescoreDiag g = mk::rescore_geometry(real, (uint32_t) qLen, (uint32_t) tLen);
+        mk::RescoreState s;
+        for (uint32_t i = 0; i < g.len; i++) s.step(mat[std::min<int>(q[g.q0 + i], 20) * 21 + std::min<int>(t[g.t0 + i], 20)], (int32_t) i);
+        mk::rescore_offer(best, s, real);
+    }
+    int ids = 0;
+    if (best.found) {
+        const mk::RescoreDiag g = mk::rescore_geometry(best.real, (uint32_t) qLen, (uint32_t) tLen);
+        for (int i = best.start; i <= best.end; i++) ids += q[g.q0 + i] == t[g.t0 + i] ? 1 : 0;
+    }
+    if (identities) *identities = (uint32_t) ids;
+    mk::Evaluer ev;
+    ev.init_gapless(dbResidues);
+    return mk::rescore_record(C, best, 0, qLen, tLen, ids, ev.evalue((double) best.score, (double) qLen), static_cast<int>(ev.bitScore((double) best.score) + 0.5), *out) ? 1 : 0;
+}
+
+int mk_rescore_diagonal(mk_targetdb *db, mk_queries *q, const mk_params *P, int rescoreMode, int sortResults) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
+    if ((rc = check_rescore(P, rescoreMode, sortResults)) != MK_OK) return rc;
+    if (q->isProfile || db->profileSearch || P->profile_search != 0)
+        return fail(MK_ERR_UNSUPPORTED, "rescorediagonal with profile queries or a profile database is not implemented (the reference refuses --alignment-mode 4 there)");
+    if (!q->havePref) return fail(MK_ERR_ARG, "mk_rescore_diagonal: the batch has no prefilter result");
+    const uint64_t n = q->nHits;
+    if (n > 0x7FFFFFFFull) return fail(MK_ERR_UNSUPPORTED, "mk_rescore_diagonal: %llu pairs in one batch (at most 2^31 - 1)", (unsigned long long) n);
+    q->btOps.clear(); q->btOff.clear(); q->btIds.clear(); q->haveBt = false; q->btLeftBand = 0;
+    q->alnStats = mk_align_stats{n, n, 0, 0, 1};
+    q->alnOff.assign((size_t) q->n + 1, 0);
+    size_t nFinal = 0;
+    if (n > 0 && q->n > 0) {
+        // e-value per (query length, score) and bit scores of the GAPLESS statistics (rescorediagonal.cpp:107), rows kept per database
+        mk::Evaluer ev;
+        ev.init_gapless(db->off[db->n]);
+        mk::AssembleTables T;
+        mk::build_assemble_tables(ev, q->off, T, &db->gaplessRows);
+        if (db->gaplessRows.size() > 8192) db->gaplessRows.clear();
+        DevBuf<double> dEval; DevBuf<int32_t> dLenIdx, dBit;
+        HIPCHK(dEval.upload(T.evalue.data(), T.evalue.size()));
+        HIPCHK(dLenIdx.upload(T.lenIdx.data(), T.lenIdx.size()));
+        HIPCHK(dBit.upload(T.bitScore.data(), T.bitScore.size()));
+        const uint32_t nq = q->n;
+        uint64_t *dHitOff = (uint64_t *) mk::dev_scratch("rescore_hitoff", ((size_t) nq + 1) * 8);
+        mk_hit *dHits = (mk_hit *) mk::dev_scratch("rescore_hits", n * sizeof(mk_hit));
+        mk::AlnRaw *dRaw = (mk::AlnRaw *) mk::dev_scratch("rescore_raw", n * sizeof(mk::AlnRaw));
+        mk_alignment *dRec = (mk_alignment *) mk::dev_scratch("rescore_rec", n * sizeof(mk_alignment));
+        mk_alignment *dFinal = (mk_alignment *) mk::dev_scratch("rescore_final", n * sizeof(mk_alignment));
+        uint8_t *dPass = (uint8_t *) mk::dev_scratch("rescore_pass", n);
+        uint32_t *dCnt = (uint32_t *) mk::dev_scratch("rescore_cnt", ((size_t) nq * 2 + 1) * 4), *dOff = dCnt ? dCnt + nq : nullptr;
+        uint32_t *dFlags = (uint32_t *) mk::dev_scratch("rescore_flags", 32);          // [0..1] flags, [2..5] two 64-bit work counters
+        uint32_t *hFlags = (uint32_t *) mk::pinned_scratch("rescore_flags_h", 32 + 8);
+        if (!dHitOff || !dHits || !dRaw || !dRec || !dFinal || !dPass || !dCnt || !dFlags || !hFlags) return fail(MK_ERR_DEVICE, "device scratch allocation failed (rescore)");
+        HIPCHK(hipMemcpyAsync(dHitOff, q->hitOff.data(), ((size_t) nq + 1) * 8, hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipMemcpyAsync(dHits, q->hits.p, n * sizeof(mk_hit), hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipMemsetAsync(dFlags, 0, 32, g_stream));
+        mk::RescoreView V;
+        V.q_res = q->dRes.p; V.q_off = q->dOff.p; V.n_queries = nq; V.t_res = db->dRes.p; V.t_off = db->dOff.p; V.n_targets = db->n; V.mat = db->dMatAln.p;
+        V.hit_off = dHitOff; V.hits = dHits; V.n_pairs = n;
+        V.evalTab = dEval.p; V.lenIdx = dLenIdx.p; V.maxLen = (uint32_t) T.lenIdx.size() - 1; V.smax = T.smax; V.bitScore = dBit.p;
+        V.crit = mk::rescore_criteria_of(*P);
+        V.raw = dRaw; V.rec = dRec; V.pass = dPass; V.flags = dFlags; V.work = (unsigned long long *) (dFlags + 2);
+        struct FlushTimers { ~FlushTimers() { timed_flush(); } } flushTimers;      // an error return below leaves no pending timer behind
+        const int th = timed_begin("rescore_diagonal", 0, 0);
+        HIPCHK(mk::launch_rescore(V, g_stream));
+        timed_end(th);
+        std::string err;
+        const int to = timed_begin("rescore_order", (double) n * (sizeof(mk::AlnRaw) + 1.0 + sizeof(mk_alignment)), 0);
+        if ((rc = mk::rescore_order_device(V, sortResults == 1, db->dKeys.p, dCnt, dOff, dFinal, g_stream, err)) != MK_OK) return fail(rc, "%s", err.c_str());
+        timed_end(to);
+        std::vector<uint32_t> cnt(nq);
+        HIPCHK(hipMemcpyAsync(hFlags, dFlags, 32, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hFlags + 8, dOff + nq, 4, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(cnt.data(), dCnt, (size_t) nq * 4, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        unsigned long long work[2];
+        std::memcpy(work, hFlags + 2, 16);
+        timed_set(th, (double) work[0], (double) work[1]);
+        timed_flush();
+        if (hFlags[1]) return fail(MK_ERR_ARG, "%u hits name a target outside the database or a diagonal that stands for no real diagonal crossing the pair's rectangle", hFlags[1]);
+        if (hFlags[0]) return fail(MK_ERR_UNSUPPORTED, "%u pairs have an ungapped score beyond the e-value table (4096 and more)", hFlags[0]);
+        nFinal = hFlags[8];
+        if (!q->alns.reserve(std::max<size_t>(nFinal, 1) * sizeof(mk_alignment), 0)) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+        if (nFinal) {
+            HIPCHK(hipMemcpyAsync(q->alns.p, dFinal, nFinal * sizeof(mk_alignment), hipMemcpyDeviceToHost, g_stream));
+            HIPCHK(hipStreamSynchronize(g_stream));
+        }
+        for (uint32_t i = 0; i < nq; i++) q->alnOff[i + 1] = q->alnOff[i] + cnt[i];
+    } else if (!q->alns.reserve(sizeof(mk_alignment), 0)) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+    q->haveAln = true;
+    if (P->add_backtrace == 1) {
+        // the operations are aln_len x M (rescorediagonal.cpp:293-299); the identities follow from the record: seq_id = identities / denominator in
+        // float, and identities <= 2^17 is the nearest integer of seq_id x denominator
+        const mk_alignment *a = (const mk_alignment *) q->alns.p;
+        q->btOff.assign(1, 0);
+        for (size_t k = 0; k < nFinal; k++) {
+            q->btOps.insert(q->btOps.end(), (size_t) a[k].aln_len, 'M');
+            q->btOff.push_back(q->btOps.size());
+            const int den = P->seq_id_mode == mk::SEQ_ID_ALN_LEN ? a[k].aln_len : (P->seq_id_mode == mk::SEQ_ID_SHORT ? std::min(a[k].q_len, a[k].db_len) : std::max(a[k].q_len, a[k].db_len));
+            q->btIds.push_back((uint32_t) ((double) a[k].seq_id * (double) den + 0.5));
+        }
+        q->haveBt = true;
+    }
     return MK_OK;
 }
 

@@ -31,6 +31,7 @@
 #include "mk_filters.hpp"
 #include "mk_kernels.hpp"
 #include "mk_limits.hpp"
+#include "mk_rescore.hpp"
 #include "mk_segsort.hpp"
 #include <algorithm>
 #include <cmath>
@@ -567,6 +568,23 @@ __global__ __launch_bounds__(256) void assemble_rank_kernel(AssembleView A, cons
     out[off[q] + rank] = a;
 }
 
+// The list order (rescorediagonal --sort-results 0), one wave per query as in limit_scan_kernel: 64 records per step, a passing record's place is
+// the number of passing records in front of it (ballot + population count)
+__global__ __launch_bounds__(256) void assemble_list_kernel(AssembleView A, const uint32_t *off, mk_alignment *out) {
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (q >= A.nq) return;
+    const auto first_at = [&](uint64_t want) { uint32_t lo = 0, hi = A.n; while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t) A.raw[mid].pair < want) lo = mid + 1; else hi = mid; } return lo; };
+    const uint32_t b = first_at(A.hitOff[q]), e = first_at(A.hitOff[q + 1]);
+    uint32_t at = off[q];
+    for (uint32_t k0 = b; k0 < e; k0 += 64) {
+        const uint32_t k = k0 + lane;
+        const bool p = k < e && A.pass[k];
+        const unsigned long long m = __ballot(p);
+        if (p) out[at + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = A.tmp[k];
+        at += (uint32_t) __popcll(m);
+    }
+}
+
 }  // namespace
 
 void build_assemble_tables(const Evaluer &ev, const std::vector<uint64_t> &qOff, AssembleTables &t, std::unordered_map<uint32_t, std::vector<double>> *rowCache) {
@@ -642,6 +660,24 @@ static int device_scan(const uint32_t *in, uint32_t n, uint32_t *out, uint32_t *
     ANULL(sums);
     hipLaunchKernelGGL(scan_sums_kernel, dim3(nb), dim3(256), 0, stream, in, n, sums);
     hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(256), 0, stream, in, n, out, (const uint32_t *) sums, total);
+    ACHK(hipGetLastError());
+    return MK_OK;
+}
+
+// the ungapped rescoring stage (mk_rescore.hip) behind its kernel: count, scan and place the passing records with the kernels of the gapped
+// stage -- one record per pair of the list, raw[k].pair = k
+int rescore_order_device(const RescoreView &V, bool sorted, const uint32_t *sortKey, uint32_t *cnt, uint32_t *off, mk_alignment *out, hipStream_t stream,
+                         std::string &err) {
+    AssembleView A{};
+    A.raw = V.raw; A.n = (uint32_t) V.n_pairs; A.hitOff = V.hit_off; A.hits = V.hits; A.nq = V.n_queries; A.q_off = V.q_off; A.t_off = V.t_off;
+    A.sortKey = sortKey; A.tmp = V.rec; A.pass = V.pass;
+    hipLaunchKernelGGL(assemble_count_kernel, dim3((V.n_queries + 255) / 256), dim3(256), 0, stream, A, cnt);
+    ACHK(hipGetLastError());
+    const int rc = device_scan(cnt, V.n_queries, off, off + V.n_queries, stream, err);
+    if (rc != MK_OK) return rc;
+    if (A.n == 0) return MK_OK;
+    if (sorted) hipLaunchKernelGGL(assemble_rank_kernel, dim3((A.n + 255) / 256), dim3(256), 0, stream, A, (const uint32_t *) off, out);
+    else hipLaunchKernelGGL(assemble_list_kernel, dim3((A.nq + 3) / 4), dim3(256), 0, stream, A, (const uint32_t *) off, out);
     ACHK(hipGetLastError());
     return MK_OK;
 }

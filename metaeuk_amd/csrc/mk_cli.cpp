@@ -79,6 +79,8 @@ const Flag FLAGS[] = {
     {"--set-gap-extend", "-1", true},
     // properties of the reference build/host being reproduced (see mk_params in the ABI header)
     {"--ref-simd", "avx2", true}, {"--ref-l2-bytes", "", true}, {"--gpu", "0", true}, {"--shard", "", true},
+    // rescorediagonal (Parameters.cpp:504-521)
+    {"--rescore-mode", "0", true}, {"--filter-hits", "0", false}, {"--include-identity", "0", false}, {"--sort-results", "0", true},
 };
 
 std::string g_failMarker;        // <out>_<rank>.failed of a sharded worker: written by die(), seen by worker 0 (which stops waiting)
@@ -654,14 +656,16 @@ int openTargetSequences(const mk::Database &tdb, const mk_params &P, TargetSide 
 }
 
 // mode: 0 = prefilter, 1 = align, 2 = search (the `search` workflow's two modules as one pipelined pass: <queryDB> <targetDB> <alignmentDB>
-// <tmpDir>, nothing written in between -- blastp.sh:70,85 without the pref_0 round trip)
+// <tmpDir>, nothing written in between -- blastp.sh:70,85 without the pref_0 round trip), 3 = rescorediagonal (align's arguments; the
+// ungapped alignment of every hit on its diagonal, rescorediagonal.cpp).  `search --alignment-mode 4` runs the prefilter and then the stage of
+// mode 3 with rescore mode 2 (Search.cpp:261, 314-315, 387), two blocking calls.
 int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
-    const bool isAlign = mode != 0, isSearch = mode == 2;
+    const bool isAlign = mode != 0, isSearch = mode == 2, isRescore = mode == 3;
     Args a;
     if (int rc = parse(argc, argv, a)) return rc;
     const size_t need = isAlign ? 4 : 3;
     if (a.pos.size() != need) {
-        fprintf(stderr, "usage: metaeuk-amd %s <i:queryDB> <i:targetDB> %s[options]\n", isSearch ? "search" : (isAlign ? "align" : "prefilter"),
+        fprintf(stderr, "usage: metaeuk-amd %s <i:queryDB> <i:targetDB> %s[options]\n", isSearch ? "search" : (isRescore ? "rescorediagonal" : (isAlign ? "align" : "prefilter")),
                 isSearch ? "<o:alignmentDB> <tmpDir> " : (isAlign ? "<i:resultDB> <o:alignmentDB> " : "<o:prefilterDB> "));
         return EXIT_FAILURE;
     }
@@ -671,9 +675,33 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     if (isAlign && a.opt.find("-e") == a.opt.end()) a.opt["-e"] = "0.001"; // Parameters.cpp:2414 (predictexons passes -e 100 explicitly)
     // the module's own default --alignment-mode 0 resolves to score-only output (Alignment.cpp:168-178), which is not built:
     // the caller has to ask for mode 2, as predictexons does (PredictExons.cpp:13)
-    if (isAlign && a.opt.find("--alignment-mode") == a.opt.end())
+    if (isAlign && !isRescore && a.opt.find("--alignment-mode") == a.opt.end())
         return die("%s needs --alignment-mode 2 or 3 (the module default, 0 = score only, is not implemented)", isSearch ? "search" : "align");
+    // the ungapped stage: `rescorediagonal --rescore-mode 2`, or `search --alignment-mode 4` (the mode is no value of mk_params: `align` and
+    // `predictexons` keep refusing it)
+    bool ungapped = isRescore;
+    if (isSearch && a.opt["--alignment-mode"] == "4") { ungapped = true; a.opt["--alignment-mode"] = "2"; }
+    if (isRescore) {
+        a.opt.erase("--alignment-mode");                          // not a flag of the module
+        auto rm = a.opt.find("--rescore-mode");
+        if (rm == a.opt.end()) return die("rescorediagonal needs --rescore-mode 2 (the module default, 0 = hamming distance, writes hit lists and is not implemented)%s");
+        if (rm->second != "2") return die("--rescore-mode %s: only 2 (ungapped alignment) is implemented; 0 and 1 write hit lists, 3 and 4 are other alignments", rm->second);
+    } else if (a.opt.count("--rescore-mode") && !ungapped) return die("--rescore-mode is a flag of rescorediagonal and of search --alignment-mode 4%s");
+    if (ungapped) {
+        // one DB on both sides makes the reference keep every self hit whatever the criteria (sameQTDB, rescorediagonal.cpp:59, 205, 322): refused, and
+        // `db` and `./db` are one DB -- the resolved paths are compared (a path that does not resolve is compared as written; opening it fails below)
+        char r0[PATH_MAX], r1[PATH_MAX];
+        const std::string p0 = realpath(a.pos[0].c_str(), r0) ? r0 : a.pos[0], p1 = realpath(a.pos[1].c_str(), r1) ? r1 : a.pos[1];
+        if (p0 == p1) return die("the ungapped alignment stage with the query DB as the target DB (the identity rule of rescorediagonal.cpp:205) is not implemented%s");
+    }
+    int sortResults = 0;
+    if (a.opt.count("--sort-results")) {
+        if (!ungapped) return die("--sort-results is a flag of rescorediagonal and of search --alignment-mode 4%s");
+        if (a.opt["--sort-results"] != "0" && a.opt["--sort-results"] != "1") return die("--sort-results %s: 0 or 1", a.opt["--sort-results"]);
+        sortResults = atoi(a.opt["--sort-results"].c_str());
+    }
     if (int rc = fillParams(a, P, gpu)) return rc;
+    if (ungapped && ((P.max_accept != INT_MAX && P.max_accept != 0) || (P.max_rejected != INT_MAX && P.max_rejected != 0))) return die("--max-accept / --max-rejected are not flags of the ungapped alignment stage%s");
     // --alignment-output-mode 1 (the per-slice `align` of the sliced profile workflow): the accepted targets' keys only
     const bool keyListOut = isAlign && a.opt.count("--alignment-output-mode") && a.opt["--alignment-output-mode"] == "1";
     if (a.opt.count("--alignment-output-mode") && a.opt["--alignment-output-mode"] != "0" && !keyListOut)
@@ -685,6 +713,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     const bool profileQueries = (qdb.dbtype & 0xFFFF) == DBTYPE_HMM_PROFILE;      // the modules as searchslicedtargetprofile.sh calls them
     if (!profileQueries && (qdb.dbtype & 0xFFFF) != mk::DBTYPE_AMINO_ACIDS) return die("only amino-acid and profile query databases are implemented%s");
     if (profileQueries && isSearch) return die("search with a profile query DB is not a workflow of the reference: use predictexons with a profile target DB, or prefilter / align / swapresults%s");
+    if (profileQueries && ungapped) return die("the ungapped alignment stage does not take profile queries (the reference refuses them, Search.cpp:262-266)%s");
     if (profileQueries) { if (int rc = refuseFiltersForProfiles(P)) return rc; P.profile_search = 1; }
     Shard sh;
     if (int rc = shardOf(a, sh, argc, argv)) return rc;
@@ -710,6 +739,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         int32_t t = -1;
         if (f) { if (fread(&t, 4, 1, f) != 1) t = -1; fclose(f); }
         if (t >= 0 && (t & 0xFFFF) == DBTYPE_HMM_PROFILE) {
+            if (ungapped) return die("the ungapped alignment stage does not take a profile target database (the reference refuses it, Search.cpp:262-266)%s");
             if (!isSearch || profileQueries) return die("a profile target database is searched by `search` / `predictexons` (the inverted sliced search), not by %s", isAlign ? "align" : "prefilter");
             if (int rc = refuseFiltersForProfiles(P)) return rc;
             // Search.cpp:357-399 takes the inverted sliced search only with --exhaustive-search 1 (predictexons sets it itself for profile targets,
@@ -807,11 +837,13 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
             // search over target splits: the prefilter of every split, the joined lists, then the alignment against the whole database
             uint64_t total = 0;
             if (int rc = splitPrefilter(Q, nq, tdbSeq, P, plan, total)) return rc;
-            if (mk_align(T, Q, &P) != MK_OK) return die("%s", mk_last_error());
+            if ((ungapped ? mk_rescore_diagonal(T, Q, &P, 2, sortResults) : mk_align(T, Q, &P)) != MK_OK) return die("%s", mk_last_error());
             hits.resize(total);
             fprintf(stderr, "search: %d target splits%s (--max-seqs %d per split, k = %d)\n", targetSplits, plan.chosen ? " [chosen from the memory limit]" : "", plan.maxSeqs, plan.kmerSize);
         } else if (isSearch) {
-            if (mk_search(T, Q, &P) != MK_OK) return die("%s", mk_last_error());
+            if (ungapped) {                                          // prefilter, then rescorediagonal --rescore-mode 2: two blocking calls
+                if (mk_prefilter(T, Q, &P) != MK_OK || mk_rescore_diagonal(T, Q, &P, 2, sortResults) != MK_OK) return die("%s", mk_last_error());
+            } else if (mk_search(T, Q, &P) != MK_OK) return die("%s", mk_last_error());
             const mk_hit *hp; const uint64_t *ho;
             mk_prefilter_result(Q, &hp, &ho);
             hits.resize(ho[nq]);                                     // (only their number is reported)
@@ -821,6 +853,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         mk::Database pdb;
         e = pdb.open(a.pos[2]);
         if (!e.empty()) return die("%s", e);
+        if (isRescore && (pdb.dbtype & 0xFFFF) == 14 /* DBTYPE_PREFILTER_REV_RES */) return die("rescorediagonal over a reversed (bi-directional) prefilter result is not implemented%s");
         std::map<uint32_t, uint32_t> qKeyToIdx, tKeyToIdx;
         for (size_t i = 0; i < nq; i++) qKeyToIdx[qdb.entries[i].key] = (uint32_t) i;
         for (size_t i = 0; i < tkeys.size(); i++) tKeyToIdx[tkeys[i]] = (uint32_t) i;
@@ -858,7 +891,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         std::vector<uint64_t> hoff(nq + 1, 0);
         for (size_t i = 0; i < nq; i++) { hits.insert(hits.end(), perQ[i].begin(), perQ[i].end()); hoff[i + 1] = hits.size(); }
         if (mk_prefilter_result_set(Q, hits.data(), hoff.data()) != MK_OK) return die("%s", mk_last_error());
-        if (mk_align(T, Q, &P) != MK_OK) return die("%s", mk_last_error());
+        if ((isRescore ? mk_rescore_diagonal(T, Q, &P, 2, sortResults) : mk_align(T, Q, &P)) != MK_OK) return die("%s", mk_last_error());
         }
         const mk_alignment *alns; const uint64_t *aoff;
         mk_align_result(Q, &alns, &aoff);
@@ -887,7 +920,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         }
         e = w.close();
         if (!e.empty()) return die("%s", e);
-        fprintf(stderr, "%s: %llu alignments calculated, %llu passed, %.2f s\n", isSearch ? "search" : "align", (unsigned long long) hits.size(), (unsigned long long) aoff[nq], now() - t0);
+        fprintf(stderr, "%s: %llu alignments calculated, %llu passed, %.2f s\n", isSearch ? "search" : (isRescore ? "rescorediagonal" : "align"), (unsigned long long) hits.size(), (unsigned long long) aoff[nq], now() - t0);
     }
     mk_queries_destroy(Q);
     if (T) mk_targetdb_destroy(T);
@@ -1601,13 +1634,14 @@ int cmdCreateIndex(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "metaeuk-amd: MI355X prefilter+align modules of `metaeuk predictexons`\n  metaeuk-amd prefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd align <queryDB> <targetDB> <prefilterDB> <alignmentDB> [flags]\n  metaeuk-amd search <queryDB> <targetDB> <alignmentDB> <tmpDir> [flags]\n  metaeuk-amd extractorfs <contigDB> <orfDB> [--min-length N] [--translate 0|1] [--aa-sibling NAME]\n  metaeuk-amd predictexons <contigsDB> <targetsDB> <calledExonsDB> <tmpDir> [flags]\n  metaeuk-amd createindex <targetsDB> <tmpDir> [-s 7.5]\n");
+        fprintf(stderr, "metaeuk-amd: MI355X prefilter+align modules of `metaeuk predictexons`\n  metaeuk-amd prefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd align <queryDB> <targetDB> <prefilterDB> <alignmentDB> [flags]\n  metaeuk-amd rescorediagonal <queryDB> <targetDB> <prefilterDB> <alignmentDB> --rescore-mode 2 [flags]\n  metaeuk-amd search <queryDB> <targetDB> <alignmentDB> <tmpDir> [flags]\n  metaeuk-amd extractorfs <contigDB> <orfDB> [--min-length N] [--translate 0|1] [--aa-sibling NAME]\n  metaeuk-amd predictexons <contigsDB> <targetsDB> <calledExonsDB> <tmpDir> [flags]\n  metaeuk-amd createindex <targetsDB> <tmpDir> [-s 7.5]\n");
         return EXIT_FAILURE;
     }
     const std::string cmd = argv[1];
     if (cmd == "prefilter") return cmdPrefilterOrAlign(0, argc, argv);
     if (cmd == "align") return cmdPrefilterOrAlign(1, argc, argv);
     if (cmd == "search") return cmdPrefilterOrAlign(2, argc, argv);
+    if (cmd == "rescorediagonal") return cmdPrefilterOrAlign(3, argc, argv);
     if (cmd == "shardinfo" && argc >= 4) {                       // <db> r/N: the worker's entry range (first, count) -- for tests and scripts
         mk::Database db;
         const std::string e = db.open(argv[2]);

@@ -426,6 +426,19 @@ void Evaluer::init(uint64_t dbResidues) {
     dbRes = static_cast<double>(dbResidues);
 }
 
+// the gapless parameter set of blosum62 (EvalueComputation.h:70-75): what the two-argument constructor of rescorediagonal.cpp:107 selects
+void Evaluer::init_gapless(uint64_t dbResidues) {
+    lambda = 0.3207378152604042354; K = 0.13904657125294345166;
+    a_J = 0.76221128839920349041; b_J = 0; a_I = a_J; b_I = b_J;
+    alpha_J = 4.5269915477182944841; beta_J = 0; alpha_I = alpha_J; beta_I = beta_J;
+    sigma = 4.5269915477182944841; tau = 0;
+    vi_y_thr = std::max(2.0 * alpha_I / lambda, 0.0);
+    vj_y_thr = std::max(2.0 * alpha_J / lambda, 0.0);
+    c_y_thr = std::max(2.0 * sigma / lambda, 0.0);
+    logK = std::log(K);
+    dbRes = static_cast<double>(dbResidues);
+}
+
 double Evaluer::evalue(double y, double qLen) const {
     const double pi = 3.1415926535897932384626433832795;
     const double norm = 1 / std::sqrt(2.0 * pi);

@@ -78,6 +78,7 @@ uint32_t kmer_cell(uint32_t addrFirst, uint32_t addrSecond);   // table cell of 
 struct Evaluer {
     double lambda, K, logK, a_I, b_I, a_J, b_J, alpha_I, beta_I, alpha_J, beta_J, sigma, tau, vi_y_thr, vj_y_thr, c_y_thr, dbRes;
     void init(uint64_t dbResidues);
+    void init_gapless(uint64_t dbResidues);     // the ungapped statistics of rescorediagonal
     double evalue(double score, double qLen) const;
     double bitScore(double score) const;
 };
