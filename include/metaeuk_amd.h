@@ -294,6 +294,22 @@ int mk_rescore_diagonal(mk_targetdb *db, mk_queries *q, const mk_params *params,
 int mk_rescore_diagonal_host(const int8_t *mat21x21, const uint8_t *q, int q_len, const uint8_t *t, int t_len, uint16_t diagonal, uint64_t db_residues,
                              const mk_params *params, int rescore_mode, mk_alignment *out, uint32_t *identities);
 
+/* ---- --alt-ali N: alternative alignments (Alignment::computeAlternativeAlignment, M/src/alignment/Alignment.cpp:399-401, 569-601).  Runs after
+ * mk_align / mk_search on the batch's alignment result and replaces it with the merged lists; mk_align_result and mk_format_alignment read it
+ * unchanged.  Every accepted record is the origin of a chain: the target with [db_start, db_end) of the origin and of the chain's accepted
+ * alternatives replaced by X is aligned again (the last aligned residue stays unmasked, as in the reference), up to alt_ali times, until a round
+ * fails the criteria of params (evalue_thr, min_aln_len, cov_thr, cov_mode, seq_id_thr).  Every origin starts from the unmasked target.  The merged
+ * list of a query is in Matcher::compareHits order; records that tie down to the DB key keep chain order (origin, then its alternatives by round).
+ * alt_ali = 0: MK_OK, the result untouched; negative or no alignment result: MK_ERR_ARG; above 32, alignment_mode 3 / add_backtrace (the backtrace
+ * of a masked target is not restated), profile queries or a profile database: MK_ERR_UNSUPPORTED. */
+int mk_alt_alignments(mk_targetdb *db, mk_queries *q, const mk_params *params, int alt_ali);
+/* the chain of ONE origin, host code without a GPU and without mk_init (the twin the kernel is checked against): mat21x21 = int8 scores
+ * (NULL: the alignment matrix), q / t = residue codes, q_bias8 = the int8 composition bias of the query's rows (NULL: none), db_residues = residues
+ * of the target database (the e-value).  Fills out[0 .. *n_out) in round order (db_key = origin->db_key). */
+int mk_alt_alignments_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int q_len, const uint8_t *t, int t_len,
+                           const mk_alignment *origin, uint64_t db_residues, const mk_params *params, int alt_ali,
+                           mk_alignment *out /* room for alt_ali */, uint32_t *n_out);
+
 /* ---- producer of the query batch: `extractorfs` + `translatenucs` (+ `reverseseq`) as predictexons runs
  * them (util/extractorfs.cpp:19-159, Orf::findAll, translatenucs.cpp:57-102; the genetic code, the start modes, the frames, the gap and
  * length limits, the contig start and end modes, the added stop marks and the null mode are mk_orf_params).  Contigs are ASCII nucleotides (IUPAC codes, lower case,

@@ -55,7 +55,7 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size",
            "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band",
            "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host", "mk_align_statistics", "mk_align_limit_scan",
-           "mk_rescore_diagonal", "mk_rescore_diagonal_host"]
+           "mk_rescore_diagonal", "mk_rescore_diagonal_host", "mk_alt_alignments", "mk_alt_alignments_host"]
 
 
 def lib():
@@ -664,6 +664,29 @@ def rescore_diagonal_host(q, t, diagonal, db_residues, params, mat=None, rescore
     if rc < 0:
         _chk(rc)
     return rc == 1, a, int(ids.value)
+
+
+# the alternative-alignment kernel: largest --alt-ali, rows of the 8-lane shape and of a row tile, columns per fetch block of the two lane shapes
+# (csrc/mk_altali.hpp)
+ALTALI_MAX, ALTALI_SMALL_ROWS, ALTALI_TILE_ROWS, ALTALI_SMALL_BLOCK, ALTALI_LARGE_BLOCK = 32, 64, 512, 32, 256
+
+
+def alt_alignments(db, q, alt_ali, params=None):
+    """--alt-ali over the batch's alignment result (mk_alt_alignments) -> the merged (ctypes array of Alignment [total], offsets uint64[n+1])"""
+    p = params or db.params
+    _chk(lib().mk_alt_alignments(db.h, q.h, C.byref(p), C.c_int(int(alt_ali))))
+    return align_result(q)
+
+
+def alt_alignments_host(q, q_bias8, t, origin, db_residues, params, alt_ali, mat=None):
+    """the chain of one origin on code arrays, host code (mk_alt_alignments_host) -> list of Alignment in round order"""
+    q = np.ascontiguousarray(q, dtype=np.uint8); t = np.ascontiguousarray(t, dtype=np.uint8)
+    b = None if q_bias8 is None else np.ascontiguousarray(q_bias8, dtype=np.int8)
+    m = None if mat is None else np.ascontiguousarray(mat, dtype=np.int8)
+    out, n = (Alignment * max(1, int(alt_ali)))(), C.c_uint32()
+    _chk(lib().mk_alt_alignments_host(None if m is None else _p(m), _p(q), None if b is None else _p(b), C.c_int(len(q)), _p(t), C.c_int(len(t)), C.byref(origin),
+                                      C.c_uint64(int(db_residues)), C.byref(params), C.c_int(int(alt_ali)), out, C.byref(n)))
+    return [out[k] for k in range(n.value)]
 
 
 def sw_pairs(db, q, q_idx, t_idx, with_start=True, params=None):

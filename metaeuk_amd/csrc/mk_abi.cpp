@@ -14,6 +14,7 @@
 #include "mk_index.hpp"
 #include "mk_prefilter.hpp"
 #include "mk_profile.hpp"
+#include "mk_altali.hpp"
 #include "mk_rescore.hpp"
 #include "mk_trace.hpp"
 
@@ -2198,6 +2199,194 @@ int mk_rescore_diagonal(mk_targetdb *db, mk_queries *q, const mk_params *P, int 
         }
         q->haveBt = true;
     }
+    return MK_OK;
+}
+
+// ---- --alt-ali (mk_altali.hpp / mk_altali.hip) --------------------------------------------------------------------------------------
+static int check_altali(const mk_params *P, int altAli, bool profiles) {
+    if (altAli > mk::ALTALI_MAX) return fail(MK_ERR_UNSUPPORTED, "--alt-ali %d: at most %d alternative alignments per accepted alignment are implemented", altAli, mk::ALTALI_MAX);
+    if (profiles) return fail(MK_ERR_UNSUPPORTED, "--alt-ali with profile queries or a profile database is not implemented");
+    if (P->alignment_mode == mk::ALIGNMENT_MODE_SCORE_COV_SEQID || P->add_backtrace == 1)
+        return fail(MK_ERR_UNSUPPORTED, "--alt-ali with --alignment-mode 3 / -a is not implemented (the backtrace of a masked target is not restated)");
+    int rc = check_filters(P, false);
+    if (rc != MK_OK) return rc;
+    return check_alignment_mode(P, false);
+}
+
+// the chain of one origin on the host: the rounds of mk_altali.hpp with the scalar pass.  Returns the number of alternatives, negative on a mismatch
+static int altali_chain_host(const int8_t *mat, const uint8_t *q, const int8_t *bias, int qLen, const uint8_t *t, int tLen, const mk_alignment &origin,
+                             const mk::Evaluer &ev, const mk::AltCriteria &C, int altAli, mk_alignment *out) {
+    std::vector<uint8_t> tm(t, t + tLen);
+    const auto mask = [&](int s, int e) { for (int pos = std::max(s, 0); pos < std::min(e, tLen); pos++) tm[(size_t) pos] = (uint8_t) mk::ALTALI_X; };
+    mask(origin.db_start, origin.db_end);
+    int n = 0;
+    for (int r = 0; r < altAli; r++) {
+        const mk::AltSw f = mk::altali_gotoh([&](int row, int col) { return mk::altali_cell(mat, q[row], bias ? (int) bias[row] : 0, tm[(size_t) col]); }, qLen, tLen, C.gapOpen, C.gapExtend);
+        if (f.score <= 0) break;
+        const double evalue = ev.evalue((double) f.score, (double) qLen);
+        if (!mk::altali_gate(C, evalue, f.end_row, f.end_col, qLen, tLen)) break;
+        const mk::AltSw b = mk::altali_gotoh([&](int row, int col) { return mk::altali_cell(mat, q[f.end_row - row], bias ? (int) bias[f.end_row - row] : 0, tm[(size_t) (f.end_col - col)]); },
+                                             f.end_row + 1, f.end_col + 1, C.gapOpen, C.gapExtend);
+        if (b.score != f.score) return -1;
+        mk_alignment a;
+        std::memset(&a, 0, sizeof(a));
+        if (!mk::altali_record(C, origin.db_key, f.score, f.end_row - b.end_row, f.end_row, f.end_col - b.end_col, f.end_col, qLen, tLen, evalue,
+                               static_cast<int>(ev.bitScore((double) f.score) + 0.5), a)) break;
+        out[n++] = a;
+        mask(a.db_start, a.db_end);
+    }
+    return n;
+}
+
+int mk_alt_alignments_host(const int8_t *mat, const uint8_t *q, const int8_t *qBias8, int qLen, const uint8_t *t, int tLen, const mk_alignment *origin,
+                           uint64_t dbResidues, const mk_params *P, int altAli, mk_alignment *out, uint32_t *nOut) {
+    if (!q || !t || !origin || !P || !nOut || qLen <= 0 || tLen <= 0 || (altAli > 0 && !out)) return fail(MK_ERR_ARG, "mk_alt_alignments_host: null argument or empty sequence");
+    *nOut = 0;
+    if (altAli < 0) return fail(MK_ERR_ARG, "--alt-ali %d: negative", altAli);
+    const int rc = check_altali(P, altAli, P->profile_search != 0);
+    if (rc != MK_OK) return rc;
+    int8_t own[441];
+    if (!mat) {
+        mk::SubMat m;
+        mk::build_submat(m, mk::MAT_BLOSUM62, 2.0f, 0.0f);
+        for (int i = 0; i < 21; i++) for (int j = 0; j < 21; j++) own[i * 21 + j] = (int8_t) m.sub[i][j];
+        mat = own;
+    }
+    mk::Evaluer ev;
+    ev.init(dbResidues);
+    const int n = altali_chain_host(mat, q, qBias8, qLen, t, tLen, *origin, ev, mk::altali_criteria_of(*P), altAli, out);
+    if (n < 0) return fail(MK_ERR_SW_MISMATCH, "Score of forward/backward SW differ");
+    *nOut = (uint32_t) n;
+    return MK_OK;
+}
+
+int mk_alt_alignments(mk_targetdb *db, mk_queries *q, const mk_params *P, int altAli) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
+    if (altAli < 0) return fail(MK_ERR_ARG, "--alt-ali %d: negative", altAli);
+    if (altAli == 0) return MK_OK;
+    if ((rc = check_altali(P, altAli, q->isProfile || db->profileSearch || P->profile_search != 0)) != MK_OK) return rc;
+    if (!q->haveAln) return fail(MK_ERR_ARG, "mk_alt_alignments: the batch has no alignment result");
+    if (q->haveBt) return fail(MK_ERR_UNSUPPORTED, "--alt-ali over a batch aligned with -a is not implemented (the backtrace of a masked target is not restated)");
+    const size_t nChains = (size_t) q->alnOff[q->n];
+    if (nChains == 0) return MK_OK;
+    if (nChains > 0x7FFFFFFFull) return fail(MK_ERR_UNSUPPORTED, "mk_alt_alignments: %llu accepted alignments in one batch (at most 2^31 - 1)", (unsigned long long) nChains);
+    const mk_alignment *orig = (const mk_alignment *) q->alns.p;
+    const uint32_t stride = (uint32_t) altAli + 1u;
+    // the chains: one per accepted record, in the order of the lists
+    std::vector<uint32_t> chainQ(nChains), chainT(nChains), nIv(nChains, 1u);
+    std::vector<mk::AltInterval> iv(nChains * stride, mk::AltInterval{0, 0});
+    uint32_t nTiled = 0;
+    bool anyLarge = false;
+    for (uint32_t i = 0; i < q->n; i++)
+        for (uint64_t k = q->alnOff[i]; k < q->alnOff[i + 1]; k++) {
+            if (orig[k].db_key >= db->n) return fail(MK_ERR_ARG, "mk_alt_alignments: alignment %llu names target %u outside the database", (unsigned long long) k, orig[k].db_key);
+            chainQ[k] = i; chainT[k] = orig[k].db_key;
+            iv[k * stride] = mk::AltInterval{orig[k].db_start, orig[k].db_end};
+            const uint64_t qLen = q->off[i + 1] - q->off[i];
+            anyLarge |= qLen > (uint64_t) mk::ALTALI_SMALL_ROWS;
+            nTiled += qLen > (uint64_t) mk::ALTALI_TILE_ROWS ? 1u : 0u;
+        }
+    const size_t borderWords = (size_t) nTiled * db->maxLen;
+    if (borderWords > (1ull << 28)) return fail(MK_ERR_UNSUPPORTED, "--alt-ali: %u alignments of queries longer than %d residues in one batch need more than 1 GB of tile scratch", nTiled, mk::ALTALI_TILE_ROWS);
+    std::shared_ptr<const ScoreTabs> tabs = score_tables(db, q, P->evalue_thr);
+    const mk::AssembleTables &T = tabs->tables;
+    DevBuf<double> dEval; DevBuf<int32_t> dLenIdx, dBit; DevBuf<uint32_t> dChainQ, dChainT, dNIv; DevBuf<mk::AltInterval> dIv;
+    HIPCHK(dEval.upload(T.evalue.data(), T.evalue.size()));
+    HIPCHK(dLenIdx.upload(T.lenIdx.data(), T.lenIdx.size()));
+    HIPCHK(dBit.upload(T.bitScore.data(), T.bitScore.size()));
+    HIPCHK(dChainQ.upload(chainQ.data(), nChains)); HIPCHK(dChainT.upload(chainT.data(), nChains)); HIPCHK(dNIv.upload(nIv.data(), nChains));
+    HIPCHK(dIv.upload(iv.data(), iv.size()));
+    uint32_t *dJobs = (uint32_t *) mk::dev_scratch("altali_jobs", nChains * 2 * 4), *dNext = dJobs ? dJobs + nChains : nullptr;
+    mk_alignment *dRec = (mk_alignment *) mk::dev_scratch("altali_rec", nChains * sizeof(mk_alignment));
+    uint8_t *dVerdict = (uint8_t *) mk::dev_scratch("altali_verdict", nChains);
+    uint32_t *dCnt = (uint32_t *) mk::dev_scratch("altali_cnt", (nChains / 256 + 2) * 4);
+    uint32_t *dBorder = (uint32_t *) mk::dev_scratch("altali_border", std::max<size_t>(borderWords, 1) * 4);
+    uint32_t *dFlags = (uint32_t *) mk::dev_scratch("altali_flags", 48);       // [0..1] flags, [2] border slots taken, [3] next round's jobs, [4..7] two 64-bit work counters
+    uint32_t *hFlags = (uint32_t *) mk::pinned_scratch("altali_flags_h", 48);
+    uint32_t *hJobs = (uint32_t *) mk::pinned_scratch("altali_jobs_h", nChains * 4);
+    uint8_t *hVerdict = (uint8_t *) mk::pinned_scratch("altali_verdict_h", nChains);
+    mk_alignment *hRec = (mk_alignment *) mk::pinned_scratch("altali_rec_h", nChains * sizeof(mk_alignment));
+    if (!dJobs || !dRec || !dVerdict || !dCnt || !dBorder || !dFlags || !hFlags || !hJobs || !hVerdict || !hRec) return fail(MK_ERR_DEVICE, "device scratch allocation failed (alt-ali)");
+    for (size_t k = 0; k < nChains; k++) hJobs[k] = (uint32_t) k;
+    HIPCHK(hipMemcpyAsync(dJobs, hJobs, nChains * 4, hipMemcpyHostToDevice, g_stream));
+    mk::AltView V;
+    V.q_res = q->dRes.p; V.q_bias8 = q->dBias8.p; V.q_off = q->dOff.p; V.t_res = db->dRes.p; V.t_off = db->dOff.p; V.mat = db->dMatAln.p;
+    V.chain_q = dChainQ.p; V.chain_t = dChainT.p; V.chain_niv = dNIv.p; V.chain_iv = dIv.p; V.iv_stride = stride;
+    V.evalTab = dEval.p; V.lenIdx = dLenIdx.p; V.maxLen = (uint32_t) T.lenIdx.size() - 1; V.smax = T.smax; V.bitScore = dBit.p;
+    V.crit = mk::altali_criteria_of(*P);
+    V.rec = dRec; V.verdict = dVerdict; V.border = dBorder; V.border_stride = db->maxLen; V.border_slots = nTiled; V.border_next = dFlags + 2;
+    V.flags = dFlags; V.work = (unsigned long long *) (dFlags + 4);
+    struct FlushTimers { ~FlushTimers() { timed_flush(); } } flushTimers;      // an error return below leaves no pending timer behind
+    std::vector<std::vector<mk_alignment>> alts(nChains);
+    std::vector<uint32_t> hostTail;                    // chains with a score beyond the e-value table
+    uint32_t nJobs = (uint32_t) nChains;
+    for (int round = 1; round <= altAli && nJobs > 0; round++) {
+        HIPCHK(hipMemsetAsync(dFlags, 0, 48, g_stream));
+        V.jobs = dJobs; V.n_jobs = nJobs;
+        const int th = timed_begin("alt_alignments", 0, 0);
+        HIPCHK(mk::launch_altali(V, anyLarge, g_stream));
+        timed_end(th);
+        const int tc = timed_begin("alt_alignments_compact", (double) nJobs * 9.0, 0);
+        HIPCHK(mk::launch_altali_compact(dJobs, dVerdict, nJobs, dCnt, dNext, dFlags + 3, g_stream));
+        timed_end(tc);
+        HIPCHK(hipMemcpyAsync(hFlags, dFlags, 48, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hJobs, dJobs, (size_t) nJobs * 4, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hVerdict, dVerdict, nJobs, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hRec, dRec, (size_t) nJobs * sizeof(mk_alignment), hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        unsigned long long work[2];
+        std::memcpy(work, hFlags + 4, 16);
+        timed_set(th, (double) work[0], (double) work[1]);
+        timed_flush();
+        if (hFlags[0]) return fail(MK_ERR_SW_MISMATCH, "Score of forward/backward SW differ for %u alternative alignments", hFlags[0]);
+        if (hFlags[1]) return fail(MK_ERR_DEVICE, "internal: %u alternative alignments found no tile scratch", hFlags[1]);
+        for (uint32_t j = 0; j < nJobs; j++) {
+            if (hVerdict[j] == mk::ALT_ACCEPTED) alts[hJobs[j]].push_back(hRec[j]);
+            else if (hVerdict[j] == mk::ALT_BEYOND_TABLE) hostTail.push_back(hJobs[j]);
+        }
+        std::swap(dJobs, dNext);
+        nJobs = hFlags[3];
+    }
+    // the host tail, as in mk_align: a chain that met a score beyond the e-value table is redone by the twin, from its first round
+    if (!hostTail.empty()) {
+        HostTimer ht("host_alt_alignments_tail");
+        std::vector<int8_t> mat(441), bias;
+        std::vector<uint8_t> t;
+        HIPCHK(hipMemcpy(mat.data(), db->dMatAln.p, 441, hipMemcpyDeviceToHost));
+        for (uint32_t c : hostTail) {
+            const uint32_t qi = chainQ[c], ti = chainT[c];
+            const int qLen = (int) (q->off[qi + 1] - q->off[qi]), tLen = (int) (db->off[ti + 1] - db->off[ti]);
+            t.resize((size_t) tLen); bias.resize((size_t) qLen);
+            HIPCHK(hipMemcpy(t.data(), db->dRes.p + db->off[ti], (size_t) tLen, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(bias.data(), q->dBias8.p + q->off[qi], (size_t) qLen, hipMemcpyDeviceToHost));
+            alts[c].assign((size_t) altAli, mk_alignment{});
+            const int n = altali_chain_host(mat.data(), q->res.data() + q->off[qi], bias.data(), qLen, t.data(), tLen, orig[c], db->evaluer, V.crit, altAli, alts[c].data());
+            if (n < 0) return fail(MK_ERR_SW_MISMATCH, "Score of forward/backward SW differ");
+            alts[c].resize((size_t) n);
+        }
+    }
+    // the merged lists: chain order (origin, then its alternatives by round), then a STABLE sort by Matcher::compareHits -- fully tied records keep
+    // chain order
+    size_t total = nChains;
+    for (const auto &a : alts) total += a.size();
+    std::vector<mk_alignment> merged;
+    merged.reserve(total);
+    std::vector<uint64_t> newOff((size_t) q->n + 1, 0);
+    for (uint32_t i = 0; i < q->n; i++) {
+        const size_t begin = merged.size();
+        for (uint64_t k = q->alnOff[i]; k < q->alnOff[i + 1]; k++) { merged.push_back(orig[k]); merged.insert(merged.end(), alts[k].begin(), alts[k].end()); }
+        std::stable_sort(merged.begin() + (ptrdiff_t) begin, merged.end(), [&](const mk_alignment &x, const mk_alignment &y) {
+            mk_alignment kx = x, ky = y;
+            if (!db->keys.empty()) { kx.db_key = db->keys[x.db_key]; ky.db_key = db->keys[y.db_key]; }
+            return mk::alignment_less(kx, ky);
+        });
+        newOff[i + 1] = merged.size();
+    }
+    if (!q->alns.reserve(std::max<size_t>(total, 1) * sizeof(mk_alignment), 0)) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+    std::memcpy(q->alns.p, merged.data(), total * sizeof(mk_alignment));
+    q->alnOff = newOff;
     return MK_OK;
 }
 

@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleView A) {
     sid = fminf(sid, 1.0f);
     a.seq_id = fmaxf(0.0f, sid);
     a.bit_score = A.bitScore[r.score];
-    A.tmp[i] = a;
+    store_record(&A.tmp[i], a);
     A.pass[i] = (a.evalue <= A.evalThr && a.aln_len >= A.minAlnLen && has_coverage(A.filter.cov_thr, A.filter.cov_mode, a.qcov, a.dbcov) &&
                  seq_id_ok(a.seq_id, A.filter.seq_id_thr)) ? 1 : 0;
 }
@@ -565,7 +565,7 @@ __global__ __launch_bounds__(256) void assemble_rank_kernel(AssembleView A, cons
         }
         rank += before ? 1u : 0u;
     }
-    out[off[q] + rank] = a;
+    store_record(&out[off[q] + rank], a);
 }
 
 // The list order (rescorediagonal --sort-results 0), one wave per query as in limit_scan_kernel: 64 records per step, a passing record's place is
@@ -580,7 +580,7 @@ __global__ __launch_bounds__(256) void assemble_list_kernel(AssembleView A, cons
         const uint32_t k = k0 + lane;
         const bool p = k < e && A.pass[k];
         const unsigned long long m = __ballot(p);
-        if (p) out[at + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = A.tmp[k];
+        if (p) store_record(&out[at + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))], A.tmp[k]);
         at += (uint32_t) __popcll(m);
     }
 }

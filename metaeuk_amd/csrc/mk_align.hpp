@@ -2,6 +2,7 @@
 // (Alignment::run's per-pair work: Matcher::getSWResult -> SmithWaterman::ssw_align, on the GPU).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -27,6 +28,15 @@ struct AlnRaw { uint32_t pair; int32_t score, q_end, t_end, q_start, t_start; };
 // q_start of a record without start positions: -2 = the reverse pass found another score (t_start holds it), ALN_SKIPPED = the coverage gate of
 // a result filter dropped the pair before the reverse pass (never accepted)
 constexpr int32_t ALN_SKIPPED = -3;
+
+// A record written by a kernel, padding included: mk_alignment has four unnamed bytes in front of its double, a struct assignment may leave them as
+// the destination held them, and the records reach the caller byte for byte -- two runs over one batch must return the same bytes
+// (tests/test_gpu_determinism.py) whatever the scratch buffers held before.
+static_assert(sizeof(mk_alignment) == 64 && offsetof(mk_alignment, evalue) == 24 && offsetof(mk_alignment, dbcov) == 16, "the padding word is dword 5");
+__device__ __forceinline__ void store_record(mk_alignment *dst, const mk_alignment &a) {
+    *dst = a;
+    reinterpret_cast<uint32_t *>(dst)[5] = 0u;
+}
 
 // e-value gate as a per-query-length table: pass(score) = score >= s0 || bit(score) for score < 256
 // (ssw_align_private's `evalue > evalueThr` early return, StripedSmithWaterman.cpp:390-398)

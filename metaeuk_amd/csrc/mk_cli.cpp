@@ -121,7 +121,8 @@ void printPrefilterStatistics(const mk_queries *Q, const mk_params &P) {
     fwrite(buf, 1, n, stderr);
 }
 
-int parse(int argc, char **argv, Args &a) {
+// altAli: the command honours --alt-ali (align and search); every other command keeps refusing a value other than the default
+int parse(int argc, char **argv, Args &a, bool altAli = false) {
     for (int i = 2; i < argc; i++) {
         const std::string s = argv[i];
         if (s.size() >= 2 && s[0] == '-' && !(s[1] >= '0' && s[1] <= '9')) {
@@ -145,6 +146,7 @@ int parse(int argc, char **argv, Args &a) {
             std::string(k.name) == "--realign-max-seqs" || std::string(k.name) == "--mask-lower-case" ||
             std::string(k.name) == "--threads" || std::string(k.name) == "--remove-tmp-files" || std::string(k.name) == "--reuse-latest" ||
             std::string(k.name) == "--force-reuse" || std::string(k.name) == "--disk-space-limit" || std::string(k.name) == "--mpi-runner") continue;    // no effect on this path
+        if (std::string(k.name) == "--alt-ali" && altAli) continue;   // read by cmdPrefilterOrAlign
         if (std::string(k.name) == "--start-sens") continue;          // only read when --sens-steps > 1, which is refused below
         if (std::string(k.name) == "--exhaustive-search") continue;   // predictexons turns it on by itself for profile targets (PredictExons.cpp:22-26); checked there
         if (std::string(k.name) == "--max-seq-len") {                 // sequences are never cut here: the value must admit everything the reference admits
@@ -662,7 +664,7 @@ int openTargetSequences(const mk::Database &tdb, const mk_params &P, TargetSide 
 int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     const bool isAlign = mode != 0, isSearch = mode == 2, isRescore = mode == 3;
     Args a;
-    if (int rc = parse(argc, argv, a)) return rc;
+    if (int rc = parse(argc, argv, a, mode == 1 || mode == 2)) return rc;
     const size_t need = isAlign ? 4 : 3;
     if (a.pos.size() != need) {
         fprintf(stderr, "usage: metaeuk-amd %s <i:queryDB> <i:targetDB> %s[options]\n", isSearch ? "search" : (isRescore ? "rescorediagonal" : (isAlign ? "align" : "prefilter")),
@@ -702,6 +704,17 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     }
     if (int rc = fillParams(a, P, gpu)) return rc;
     if (ungapped && ((P.max_accept != INT_MAX && P.max_accept != 0) || (P.max_rejected != INT_MAX && P.max_rejected != 0))) return die("--max-accept / --max-rejected are not flags of the ungapped alignment stage%s");
+    // --alt-ali N (Alignment.cpp:399-401): the alternative alignments of every accepted record, a stage behind mk_align / mk_search (mk_alt_alignments)
+    int altAli = 0;
+    if (a.opt.count("--alt-ali")) {
+        char *end;
+        const long v = strtol(a.opt["--alt-ali"].c_str(), &end, 10);
+        if (*end != 0 || end == a.opt["--alt-ali"].c_str() || v < 0 || v > INT_MAX) return die("--alt-ali %s: a number of alternative alignments, 0 or more", a.opt["--alt-ali"]);
+        altAli = (int) v;
+    }
+    if (altAli > 0 && ungapped) return die("--alt-ali is not a flag of the ungapped alignment stage%s");
+    if (altAli > 0 && (P.add_backtrace != 0 || P.alignment_mode == 3))
+        return die("--alt-ali with -a / --alignment-mode 3 is not implemented (the backtrace of a masked target is not restated)%s");
     // --alignment-output-mode 1 (the per-slice `align` of the sliced profile workflow): the accepted targets' keys only
     const bool keyListOut = isAlign && a.opt.count("--alignment-output-mode") && a.opt["--alignment-output-mode"] == "1";
     if (a.opt.count("--alignment-output-mode") && a.opt["--alignment-output-mode"] != "0" && !keyListOut)
@@ -714,6 +727,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     if (!profileQueries && (qdb.dbtype & 0xFFFF) != mk::DBTYPE_AMINO_ACIDS) return die("only amino-acid and profile query databases are implemented%s");
     if (profileQueries && isSearch) return die("search with a profile query DB is not a workflow of the reference: use predictexons with a profile target DB, or prefilter / align / swapresults%s");
     if (profileQueries && ungapped) return die("the ungapped alignment stage does not take profile queries (the reference refuses them, Search.cpp:262-266)%s");
+    if (profileQueries && altAli > 0) return die("--alt-ali with a profile query database is not implemented%s");
     if (profileQueries) { if (int rc = refuseFiltersForProfiles(P)) return rc; P.profile_search = 1; }
     Shard sh;
     if (int rc = shardOf(a, sh, argc, argv)) return rc;
@@ -740,6 +754,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         if (f) { if (fread(&t, 4, 1, f) != 1) t = -1; fclose(f); }
         if (t >= 0 && (t & 0xFFFF) == DBTYPE_HMM_PROFILE) {
             if (ungapped) return die("the ungapped alignment stage does not take a profile target database (the reference refuses it, Search.cpp:262-266)%s");
+            if (altAli > 0) return die("--alt-ali with a profile target database is not implemented%s");
             if (!isSearch || profileQueries) return die("a profile target database is searched by `search` / `predictexons` (the inverted sliced search), not by %s", isAlign ? "align" : "prefilter");
             if (int rc = refuseFiltersForProfiles(P)) return rc;
             // Search.cpp:357-399 takes the inverted sliced search only with --exhaustive-search 1 (predictexons sets it itself for profile targets,
@@ -893,6 +908,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         if (mk_prefilter_result_set(Q, hits.data(), hoff.data()) != MK_OK) return die("%s", mk_last_error());
         if ((isRescore ? mk_rescore_diagonal(T, Q, &P, 2, sortResults) : mk_align(T, Q, &P)) != MK_OK) return die("%s", mk_last_error());
         }
+        if (altAli > 0 && mk_alt_alignments(T, Q, &P, altAli) != MK_OK) return die("%s", mk_last_error());
         const mk_alignment *alns; const uint64_t *aoff;
         mk_align_result(Q, &alns, &aoff);
         // -a: the 11th column, Matcher::compressAlignment of the backtrace (Matcher.cpp:312-317)
