@@ -294,6 +294,26 @@ int mk_rescore_diagonal(mk_targetdb *db, mk_queries *q, const mk_params *params,
 int mk_rescore_diagonal_host(const int8_t *mat21x21, const uint8_t *q, int q_len, const uint8_t *t, int t_len, uint16_t diagonal, uint64_t db_residues,
                              const mk_params *params, int rescore_mode, mk_alignment *out, uint32_t *identities);
 
+/* ---- ungappedprefilter: the exhaustive gapless prefilter, the front end `search --prefilter-mode 1` runs in place of the k-mer prefilter
+ * (M/src/prefiltering/ungappedprefilter.cpp:338-477 with alignmentMode 0, SmithWaterman::ungapped_alignment, StripedSmithWaterman.cpp:1722-1781;
+ * Search.cpp:323-350).  Every query is scored against every target: the best gapless local alignment over all diagonals in the reference's
+ * saturating byte arithmetic (alignment matrix, the query's composition bias, the unmasked target residues), capped at 255 - bias.  A pair that
+ * fails Util::canBeCovered(cov_thr, cov_mode) is skipped, a hit is kept when score > min_ungapped_score (strictly), and a query keeps its first
+ * max_seqs hits in hit_t::compareHitsByScoreAndId order (score descending, then the DB key of mk_targetdb_set_keys -- the target index without
+ * keys -- ascending).  Fills the batch's PREFILTER result: mk_prefilter_result, mk_align, mk_rescore_diagonal and the formatters read it unchanged
+ * (seq_id = target index, diagonal 0).  No k-mer index is needed: works on mk_targetdb_create_sequences and mk_targetdb_create databases.  Honoured
+ * of params: max_seqs, min_ungapped_score, comp_bias_corr, comp_bias_scale, cov_thr, cov_mode.  When comp_bias_corr / comp_bias_scale differ from
+ * the values the batch was created with, the call derives the composition bias it scores with into scratch memory of its own; the batch, and what
+ * every other stage reads from it, stays as mk_queries_create made it.  Precondition: residue codes 0 .. 20 on both sides, as mk_encode yields
+ * them (the kernel looks a target code up modulo 32 and keeps code 31 for window positions outside the target; the twin reads every code above
+ * 20 as X -- larger codes are scored differently by the two).  MK_ERR_UNSUPPORTED: profile queries or a profile
+ * database, a database opened from an index DB (its lookup is the masked one), a negative min_ungapped_score. */
+int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *params);
+/* the score of ONE pair, host code without a GPU and without mk_init (the twin the kernel is checked against): cell by cell in the literal
+ * unsigned-byte steps.  mat21x21 = int8 scores [t * 21 + q] (NULL: the alignment matrix), q / t = residue codes, q_bias8 = the int8 composition
+ * bias of the query's rows (NULL: none; what mk_queries_derived reports as sw_bias8).  q_len >= 1, t_len >= 0. */
+int mk_ungapped_prefilter_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int q_len, const uint8_t *t, int t_len, int *score);
+
 /* ---- --alt-ali N: alternative alignments (Alignment::computeAlternativeAlignment, M/src/alignment/Alignment.cpp:399-401, 569-601).  Runs after
  * mk_align / mk_search on the batch's alignment result and replaces it with the merged lists; mk_align_result and mk_format_alignment read it
  * unchanged.  Every accepted record is the origin of a chain: the target with [db_start, db_end) of the origin and of the chain's accepted

@@ -35,6 +35,11 @@ size_t mk_debug_params_size(void);
  * backtrace: aln_len stays the mode-2 value, 0 identities -- DESIGN.md, the backtrace stage); the tests assert 0 on their inputs */
 uint64_t mk_debug_trace_left_band(const mk_queries *q);
 
+/* the work split of the gapless prefilter's kernel (metaeuk_amd/csrc/mk_ungapped.hpp): diagonals per lane, queries per packed lookup, rows of the
+ * profile image, lanes per target for short and for long targets, the target length from which the long shape is used.  The tests place their
+ * edge cases with these, so a change of the header moves them */
+void mk_debug_ungapped_constants(int out[6]);
+
 /* ---- experiment hook (tools/micro/mk_experiments.hip is its only user): the device view of a (database, batch) pair -- a
  * mk::PrefilterDeviceView (metaeuk_amd/csrc/mk_prefilter.hpp: pointers into HBM, valid while both handles live) copied into view_out, whose
  * size must be given as view_bytes -- and the batch's host offsets.  The layout of that struct is NOT stable across builds. */

@@ -55,7 +55,8 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_format_prefilter_statistics", "mk_device_memory", "mk_result_filter", "mk_debug_params_size",
            "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band",
            "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host", "mk_align_statistics", "mk_align_limit_scan",
-           "mk_rescore_diagonal", "mk_rescore_diagonal_host", "mk_alt_alignments", "mk_alt_alignments_host"]
+           "mk_rescore_diagonal", "mk_rescore_diagonal_host", "mk_alt_alignments", "mk_alt_alignments_host",
+           "mk_ungapped_prefilter", "mk_ungapped_prefilter_host", "mk_debug_ungapped_constants"]
 
 
 def lib():
@@ -664,6 +665,38 @@ def rescore_diagonal_host(q, t, diagonal, db_residues, params, mat=None, rescore
     if rc < 0:
         _chk(rc)
     return rc == 1, a, int(ids.value)
+
+
+# the gapless prefilter's work split: diagonals per lane, queries per packed lookup, rows of the profile image, lanes per target for short and for
+# long targets, the target length from which the long shape is used -- read from the library (csrc/mk_ungapped.hpp), never copied
+_UNG_NAMES = ("UNG_DIAGS", "UNG_PACK", "UNG_ROW_TILE", "UNG_GROUP_SHORT", "UNG_GROUP_LONG", "UNG_LONG_TARGET")
+
+
+def __getattr__(name):
+    if name in _UNG_NAMES:
+        v = (C.c_int * 6)()
+        lib().mk_debug_ungapped_constants(v)
+        return int(v[_UNG_NAMES.index(name)])
+    raise AttributeError(name)
+
+
+def ungapped_prefilter(db, q, params=None):
+    """ungappedprefilter / --prefilter-mode 1 over the batch (mk_ungapped_prefilter) -> (hits structured array [total], offsets uint64[n+1])"""
+    p = params or db.params
+    _chk(lib().mk_ungapped_prefilter(db.h, q.h, C.byref(p)))
+    return prefilter_result(q)
+
+
+def ungapped_prefilter_host(q, t, q_bias8=None, mat=None):
+    """the score of one pair of code arrays in the literal byte arithmetic, host code (mk_ungapped_prefilter_host)"""
+    q = np.ascontiguousarray(q, dtype=np.uint8); t = np.ascontiguousarray(t, dtype=np.uint8)
+    b = None if q_bias8 is None else np.ascontiguousarray(q_bias8, dtype=np.int8)
+    m = None if mat is None else np.ascontiguousarray(mat, dtype=np.int8)
+    tt = t if len(t) else np.zeros(1, dtype=np.uint8)
+    score = C.c_int()
+    _chk(lib().mk_ungapped_prefilter_host(None if m is None else _p(m), _p(q), None if b is None else _p(b), C.c_int(len(q)), _p(tt), C.c_int(len(t)),
+                                          C.byref(score)))
+    return int(score.value)
 
 
 # the alternative-alignment kernel: largest --alt-ali, rows of the 8-lane shape and of a row tile, columns per fetch block of the two lane shapes

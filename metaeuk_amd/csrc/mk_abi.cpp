@@ -17,6 +17,7 @@
 #include "mk_altali.hpp"
 #include "mk_rescore.hpp"
 #include "mk_trace.hpp"
+#include "mk_ungapped.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -283,6 +284,12 @@ struct mk_targetdb {
     DevBuf<uint16_t> dIndex2, dNum3; // ... their numbers; address code -> 3-mer number
     bool profileSearch = false;      // built for profile queries (mk_params.profile_search)
     bool unindexed = false;          // mk_targetdb_create_sequences: residues only, what mk_align needs (no masking, no k-mer index)
+    bool fromIndex = false;          // mk_targetdb_open_index
+    // mk_ungapped_prefilter, made on first use: the targets by ascending length (and those lengths), with DB keys the rank of every target's key
+    // among all keys and its inverse (mk_targetdb_set_keys drops them)
+    std::vector<uint32_t> ungLens;
+    DevBuf<uint32_t> dUngOrder, dUngKeyRank, dUngRankIdx;
+    bool ungOrderReady = false, ungKeysReady = false;
     std::vector<int32_t> bitScoreTable;   // static_cast<int>(bitScore(score) + 0.5), score < 32768
     // score tables of the alignment stage, kept from call to call: the e-value row of a query length depends on the database alone, and
     // consecutive batches of ORF fragments bring the same lengths (a batch of other lengths adds its rows; the device copy follows the id)
@@ -660,6 +667,7 @@ static int targetdb_create(const uint8_t *residues, const uint64_t *offsets, uin
         db->maxLen = std::max<uint32_t>(db->maxLen, (uint32_t) L);
     }
     db->profileSearch = P->profile_search != 0;
+    db->fromIndex = prebuilt != nullptr;
     if (db->profileSearch && prebuilt) { delete db; return fail(MK_ERR_UNSUPPORTED, "a precomputed index cannot serve profile queries: it was masked with the seed matrix's background and filtered by the sequence threshold"); }
     // profile queries: kmerSubMat is --sub-mat x8 (only the background of the masking uses it), Prefiltering.cpp:72-76
     mk::build_submat(db->kmerMat, db->profileSearch ? mk::MAT_BLOSUM62 : mk::MAT_VTML80, 8.0f, -0.2f);     // Prefiltering.cpp:68
@@ -934,6 +942,7 @@ int mk_targetdb_set_keys(mk_targetdb *db, const uint32_t *keys, uint32_t n) {
     if (rc) return rc;
     if (!db || !keys || n != db->n) return fail(MK_ERR_ARG, "mk_targetdb_set_keys: one key per target");
     db->keys.assign(keys, keys + n);
+    db->ungKeysReady = false;
     HIPCHK(db->dKeys.upload(keys, n));
     HIPCHK(hipStreamSynchronize(g_stream));
     return MK_OK;
@@ -2200,6 +2209,194 @@ int mk_rescore_diagonal(mk_targetdb *db, mk_queries *q, const mk_params *P, int 
         q->haveBt = true;
     }
     return MK_OK;
+}
+
+// ---- ungappedprefilter / --prefilter-mode 1 (mk_ungapped.hpp / mk_ungapped.hip) --------------------------------------------------------
+int mk_ungapped_prefilter_host(const int8_t *mat, const uint8_t *q, const int8_t *qBias8, int qLen, const uint8_t *t, int tLen, int *score) {
+    if (!q || !score || qLen <= 0 || tLen < 0 || (!t && tLen > 0)) return fail(MK_ERR_ARG, "mk_ungapped_prefilter_host: null argument, empty query or negative length");
+    int8_t own[441];
+    if (!mat) {
+        mk::SubMat m;
+        mk::build_submat(m, mk::MAT_BLOSUM62, 2.0f, 0.0f);
+        for (int i = 0; i < 21; i++) for (int j = 0; j < 21; j++) own[i * 21 + j] = (int8_t) m.sub[i][j];
+        mat = own;
+    }
+    *score = mk::ungapped_pair_host(mat, q, qBias8, qLen, t, tLen);
+    return MK_OK;
+}
+
+// the composition bias this call scores with.  A batch carries the bias of the --comp-bias-corr / --comp-bias-corr-scale it was created with, and
+// every other stage reads that one; a call that brings other values gets its own derivation in scratch memory -- the batch is not touched
+static int ungapped_comp_bias(const mk_queries *q, const mk_params *P, const int8_t **bias8) {
+    const mk_params &D = q->derivedWith;
+    const bool on = P->comp_bias_corr != 0;
+    *bias8 = q->dBias8.p;
+    const uint64_t total = q->off[q->n];
+    if (total == 0 || (on == (D.comp_bias_corr != 0) && (!on || P->comp_bias_scale == D.comp_bias_scale))) return MK_OK;
+    int16_t *kthr = (int16_t *) mk::dev_scratch("ungapped_derive_kthr", total * 2);
+    int8_t *corr = (int8_t *) mk::dev_scratch("ungapped_derive_corr", total), *sw8 = (int8_t *) mk::dev_scratch("ungapped_derive_bias8", total);
+    if (!kthr || !corr || !sw8) return fail(MK_ERR_DEVICE, "device scratch allocation failed (ungapped prefilter, composition bias)");
+    mk::SubMat kmerMat, alnMat;
+    mk::build_submat(kmerMat, mk::MAT_VTML80, 8.0f, -0.2f);
+    mk::build_submat(alnMat, mk::MAT_BLOSUM62, 2.0f, 0.0f);
+    HIPCHK(mk::launch_derive(q->dRes.p, q->dOff.p, q->n, total, kmerMat, alnMat,
+                             q->kmerSize == 7 ? mk::kmer_threshold_k7(D.sensitivity, D.kmer_score) : mk::kmer_threshold(D.sensitivity, D.kmer_score),
+                             on, P->comp_bias_scale, kthr, corr, sw8, g_stream, q->kmerSize));
+    *bias8 = sw8;
+    return MK_OK;
+}
+
+// the orders of the target side, once per database: by ascending length (the groups of a wave finish together), and by DB key (the tie order of the cut)
+static int ungapped_target_orders(mk_targetdb *db) {
+    const uint32_t n = db->n;
+    if (!db->ungOrderReady) {
+        std::vector<uint32_t> order(n);
+        for (uint32_t i = 0; i < n; i++) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return db->off[a + 1] - db->off[a] < db->off[b + 1] - db->off[b]; });
+        db->ungLens.resize(n);
+        for (uint32_t i = 0; i < n; i++) db->ungLens[i] = (uint32_t) (db->off[order[i] + 1] - db->off[order[i]]);
+        HIPCHK(db->dUngOrder.upload(order.data(), n));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        db->ungOrderReady = true;
+    }
+    if (!db->ungKeysReady) {
+        db->dUngKeyRank.drop(); db->dUngRankIdx.drop();
+        if (!db->keys.empty()) {
+            std::vector<uint32_t> byKey(n), rank(n);
+            for (uint32_t i = 0; i < n; i++) byKey[i] = i;
+            std::stable_sort(byKey.begin(), byKey.end(), [&](uint32_t a, uint32_t b) { return db->keys[a] < db->keys[b]; });
+            for (uint32_t r = 0; r < n; r++) rank[byKey[r]] = r;
+            HIPCHK(db->dUngKeyRank.upload(rank.data(), n));
+            HIPCHK(db->dUngRankIdx.upload(byKey.data(), n));
+            HIPCHK(hipStreamSynchronize(g_stream));
+        }
+        db->ungKeysReady = true;
+    }
+    return MK_OK;
+}
+
+int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
+    if (q->isProfile || db->profileSearch || P->profile_search != 0)
+        return fail(MK_ERR_UNSUPPORTED, "ungappedprefilter with profile queries or a profile database is not implemented");
+    if (db->fromIndex)
+        return fail(MK_ERR_UNSUPPORTED, "ungappedprefilter against an index DB is not implemented (its sequence lookup is the masked one): pass the sequence DB");
+    if ((rc = check_filters(P, false)) != MK_OK) return rc;
+    if (P->max_seqs < 1) return fail(MK_ERR_ARG, "--max-seqs %d: a positive number is expected", P->max_seqs);
+    if (P->min_ungapped_score < 0)
+        return fail(MK_ERR_UNSUPPORTED, "--min-ungapped-score %d: a negative threshold keeps pairs of score 0, which the score array does not tell from skipped pairs", P->min_ungapped_score);
+    const int8_t *bias8 = nullptr;
+    if ((rc = ungapped_comp_bias(q, P, &bias8)) != MK_OK) return rc;
+    if ((rc = ungapped_target_orders(db)) != MK_OK) return rc;
+    const uint32_t nq = q->n, nt = db->n, maxSeqs = (uint32_t) std::min<int64_t>(P->max_seqs, std::max<uint32_t>(nt, 1));
+    q->pfStats = mk::PrefilterStats();
+    q->hitOff.assign((size_t) nq + 1, 0);
+    q->nHits = 0;
+    if (nq == 0 || nt == 0) {
+        if (!q->hits.reserve(sizeof(mk_hit), 0)) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+        q->havePref = true;
+        return MK_OK;
+    }
+    // queries by ascending length: four neighbours share one lookup
+    std::vector<uint32_t> qOrder(nq);
+    for (uint32_t i = 0; i < nq; i++) qOrder[i] = i;
+    std::stable_sort(qOrder.begin(), qOrder.end(), [&](uint32_t a, uint32_t b) { return q->off[a + 1] - q->off[a] < q->off[b + 1] - q->off[b]; });
+    // the score array: [queries of the chunk][targets of the chunk] bytes within the budget (MK_UNGAPPED_SCORE_BUDGET, bytes, shrinks it for the tests)
+    uint64_t budget = mk::UNG_SCORE_BUDGET;
+    if (const char *k = mk::knob("MK_UNGAPPED_SCORE_BUDGET")) budget = std::max<uint64_t>(strtoull(k, nullptr, 10), mk::UNG_PACK);
+    int forceGroup = 0;
+    if (const char *k = mk::knob("MK_UNGAPPED_GROUP")) forceGroup = atoi(k);
+    if (forceGroup != 0 && forceGroup != mk::UNG_GROUP_SHORT && forceGroup != mk::UNG_GROUP_LONG)
+        return fail(MK_ERR_ARG, "MK_UNGAPPED_GROUP=%d: %d or %d lanes per target", forceGroup, mk::UNG_GROUP_SHORT, mk::UNG_GROUP_LONG);
+    const uint32_t nsC = (uint32_t) std::min<uint64_t>(nt, std::max<uint64_t>(1, budget / mk::UNG_PACK));
+    uint64_t nqC64 = std::max<uint64_t>(mk::UNG_PACK, budget / nsC / mk::UNG_PACK * mk::UNG_PACK);
+    nqC64 = std::min<uint64_t>(nqC64, std::max<uint64_t>(mk::UNG_PACK, ((16ull << 20) / maxSeqs) / mk::UNG_PACK * mk::UNG_PACK));     // (the hit block of a chunk)
+    const uint32_t nqC = (uint32_t) std::min<uint64_t>(std::min<uint64_t>(nqC64, 65535ull * mk::UNG_PACK), ((uint64_t) nq + mk::UNG_PACK - 1) / mk::UNG_PACK * mk::UNG_PACK);
+
+    uint32_t *dQOrder = (uint32_t *) mk::dev_scratch("ungapped_qorder", (size_t) nq * 4);
+    uint8_t *dCaps = (uint8_t *) mk::dev_scratch("ungapped_caps", nq);
+    uint8_t *dScores = (uint8_t *) mk::dev_scratch("ungapped_scores", (size_t) nqC * nsC);
+    uint64_t *dCand = (uint64_t *) mk::dev_scratch("ungapped_cand", (size_t) nqC * maxSeqs * 8), *dTmp = (uint64_t *) mk::dev_scratch("ungapped_tmp", (size_t) nqC * maxSeqs * 8);
+    mk_hit *dHits = (mk_hit *) mk::dev_scratch("ungapped_hits", (size_t) nqC * maxSeqs * sizeof(mk_hit));
+    uint32_t *dCnt = (uint32_t *) mk::dev_scratch("ungapped_cnt", (size_t) nqC * 8 + 16), *dHitCnt = dCnt ? dCnt + nqC : nullptr;
+    unsigned long long *dWork = dCnt ? (unsigned long long *) (dCnt + 2 * (size_t) nqC) : nullptr;
+    mk_hit *hHits = (mk_hit *) mk::pinned_scratch("ungapped_hits_h", (size_t) nqC * maxSeqs * sizeof(mk_hit));
+    uint32_t *hCnt = (uint32_t *) mk::pinned_scratch("ungapped_cnt_h", (size_t) nqC * 4 + 16);
+    if (!dQOrder || !dCaps || !dScores || !dCand || !dTmp || !dHits || !dCnt || !hHits || !hCnt) return fail(MK_ERR_DEVICE, "device scratch allocation failed (ungapped prefilter)");
+    HIPCHK(hipMemcpyAsync(dQOrder, qOrder.data(), (size_t) nq * 4, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemsetAsync(dWork, 0, 16, g_stream));
+
+    mk::UngappedView V;
+    V.q_res = q->dRes.p; V.q_off = q->dOff.p; V.q_bias8 = bias8; V.n_queries = nq; V.q_order = dQOrder; V.q_cap = dCaps;
+    V.t_res = db->dRes.p; V.t_off = db->dOff.p; V.n_targets = nt; V.t_order = db->dUngOrder.p;
+    V.mat = db->dMatAln.p;                       // [q * 21 + t]; the kernel reads [t * 21 + q]: the alignment matrix is symmetric
+    V.mat_min = 0;
+    for (int i = 0; i < 21; i++) for (int j = 0; j < 21; j++) V.mat_min = std::min<int>(V.mat_min, (int8_t) db->alnMat.sub[i][j]);
+    V.cov_thr = P->cov_thr; V.cov_mode = P->cov_mode;
+    V.scores = dScores; V.work = dWork;
+    V.q0 = V.nq = V.s0 = V.ns = 0;
+    mk::UngappedSelect S;
+    S.key_rank = db->dUngKeyRank.p; S.rank_idx = db->dUngRankIdx.p; S.min_score = P->min_ungapped_score; S.max_seqs = maxSeqs;
+    S.cand = dCand; S.cand_cnt = dCnt; S.tmp = dTmp; S.hits = dHits; S.hit_cnt = dHitCnt; S.last = false;
+
+    struct FlushTimers { ~FlushTimers() { timed_flush(); } } flushTimers;
+    HostTimer ht("host_ungapped_prefilter_total");
+    HIPCHK(mk::launch_ungapped_caps(V, dCaps, g_stream));
+    std::vector<mk_hit> staged;                      // the chunks' lists in the order of qOrder
+    std::vector<uint32_t> cnt(nq, 0);
+    // one timer per (query chunk, target chunk); the work counters run over the whole call and are read once, so the LAST timer carries the bytes
+    // and cells of all chunks -- mk_kernel_stats sums the records of a name, which is how they are read
+    int lastScoreTimer = -1;
+    for (uint32_t q0 = 0; q0 < nq; q0 += nqC) {
+        V.q0 = q0; V.nq = std::min(nqC, nq - q0);
+        HIPCHK(hipMemsetAsync(dCnt, 0, (size_t) V.nq * 4, g_stream));
+        for (uint32_t s0 = 0; s0 < nt; s0 += nsC) {
+            V.s0 = s0; V.ns = std::min(nsC, nt - s0);
+            // the long targets of the chunk (the tail of the length order) get a whole wave each
+            uint32_t split = (uint32_t) (std::lower_bound(db->ungLens.begin() + s0, db->ungLens.begin() + s0 + V.ns, (uint32_t) mk::UNG_LONG_TARGET) - (db->ungLens.begin() + s0));
+            if (forceGroup == mk::UNG_GROUP_SHORT) split = V.ns;
+            if (forceGroup == mk::UNG_GROUP_LONG) split = 0;
+            const int th = lastScoreTimer = timed_begin("ungapped_prefilter", 0, 0);
+            HIPCHK(mk::launch_ungapped_scores(V, 0, split, mk::UNG_GROUP_SHORT, g_stream));
+            HIPCHK(mk::launch_ungapped_scores(V, split, V.ns, mk::UNG_GROUP_LONG, g_stream));
+            timed_end(th);
+            S.last = s0 + V.ns == nt;
+            const int ts = timed_begin("ungapped_select", (double) V.nq * V.ns * 6.0, 0);
+            HIPCHK(mk::launch_ungapped_select(V, S, g_stream));
+            timed_end(ts);
+        }
+        HIPCHK(hipMemcpyAsync(hCnt, dHitCnt, (size_t) V.nq * 4, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hHits, dHits, (size_t) V.nq * maxSeqs * sizeof(mk_hit), hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        for (uint32_t r = 0; r < V.nq; r++) {
+            if (hCnt[r] > maxSeqs) return fail(MK_ERR_DEVICE, "ungapped prefilter: a list of %u hits (at most %u)", hCnt[r], maxSeqs);
+            cnt[qOrder[q0 + r]] = hCnt[r];
+            staged.insert(staged.end(), hHits + (size_t) r * maxSeqs, hHits + (size_t) r * maxSeqs + hCnt[r]);
+        }
+    }
+    HIPCHK(hipMemcpyAsync(hCnt, dWork, 16, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    unsigned long long work[2];
+    std::memcpy(work, hCnt, 16);
+    timed_set(lastScoreTimer, (double) work[0], (double) work[1]);
+    for (uint32_t i = 0; i < nq; i++) q->hitOff[i + 1] = q->hitOff[i] + cnt[i];
+    q->nHits = q->hitOff[nq];
+    if (!q->hits.reserve(std::max<size_t>(q->nHits, 1) * sizeof(mk_hit), 0)) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+    size_t at = 0;
+    for (uint32_t r = 0; r < nq; r++) {                  // staged list r belongs to query qOrder[r]
+        const uint32_t qi = qOrder[r];
+        if (cnt[qi]) std::memcpy((mk_hit *) q->hits.p + q->hitOff[qi], staged.data() + at, (size_t) cnt[qi] * sizeof(mk_hit));
+        at += cnt[qi];
+    }
+    q->havePref = true;
+    return MK_OK;
+}
+
+// the kernel's work split as the tests read it (metaeuk_amd_debug.h)
+void mk_debug_ungapped_constants(int out[6]) {
+    out[0] = mk::UNG_DIAGS; out[1] = mk::UNG_PACK; out[2] = mk::UNG_ROW_TILE; out[3] = mk::UNG_GROUP_SHORT; out[4] = mk::UNG_GROUP_LONG; out[5] = mk::UNG_LONG_TARGET;
 }
 
 // ---- --alt-ali (mk_altali.hpp / mk_altali.hip) --------------------------------------------------------------------------------------

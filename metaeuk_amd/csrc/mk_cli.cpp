@@ -81,6 +81,8 @@ const Flag FLAGS[] = {
     {"--ref-simd", "avx2", true}, {"--ref-l2-bytes", "", true}, {"--gpu", "0", true}, {"--shard", "", true},
     // rescorediagonal (Parameters.cpp:504-521)
     {"--rescore-mode", "0", true}, {"--filter-hits", "0", false}, {"--include-identity", "0", false}, {"--sort-results", "0", true},
+    // search (Parameters.cpp: PARAM_PREF_MODE): 1 = the exhaustive gapless prefilter; read by `search` alone
+    {"--prefilter-mode", "0", false},
 };
 
 std::string g_failMarker;        // <out>_<rank>.failed of a sharded worker: written by die(), seen by worker 0 (which stops waiting)
@@ -122,7 +124,7 @@ void printPrefilterStatistics(const mk_queries *Q, const mk_params &P) {
 }
 
 // altAli: the command honours --alt-ali (align and search); every other command keeps refusing a value other than the default
-int parse(int argc, char **argv, Args &a, bool altAli = false) {
+int parse(int argc, char **argv, Args &a, bool altAli = false, bool prefMode = false) {
     for (int i = 2; i < argc; i++) {
         const std::string s = argv[i];
         if (s.size() >= 2 && s[0] == '-' && !(s[1] >= '0' && s[1] <= '9')) {
@@ -147,6 +149,7 @@ int parse(int argc, char **argv, Args &a, bool altAli = false) {
             std::string(k.name) == "--threads" || std::string(k.name) == "--remove-tmp-files" || std::string(k.name) == "--reuse-latest" ||
             std::string(k.name) == "--force-reuse" || std::string(k.name) == "--disk-space-limit" || std::string(k.name) == "--mpi-runner") continue;    // no effect on this path
         if (std::string(k.name) == "--alt-ali" && altAli) continue;   // read by cmdPrefilterOrAlign
+        if (std::string(k.name) == "--prefilter-mode" && prefMode) continue;   // read by cmdPrefilterOrAlign (search)
         if (std::string(k.name) == "--start-sens") continue;          // only read when --sens-steps > 1, which is refused below
         if (std::string(k.name) == "--exhaustive-search") continue;   // predictexons turns it on by itself for profile targets (PredictExons.cpp:22-26); checked there
         if (std::string(k.name) == "--max-seq-len") {                 // sequences are never cut here: the value must admit everything the reference admits
@@ -660,14 +663,42 @@ int openTargetSequences(const mk::Database &tdb, const mk_params &P, TargetSide 
 // mode: 0 = prefilter, 1 = align, 2 = search (the `search` workflow's two modules as one pipelined pass: <queryDB> <targetDB> <alignmentDB>
 // <tmpDir>, nothing written in between -- blastp.sh:70,85 without the pref_0 round trip), 3 = rescorediagonal (align's arguments; the
 // ungapped alignment of every hit on its diagonal, rescorediagonal.cpp).  `search --alignment-mode 4` runs the prefilter and then the stage of
-// mode 3 with rescore mode 2 (Search.cpp:261, 314-315, 387), two blocking calls.
+// mode 3 with rescore mode 2 (Search.cpp:261, 314-315, 387), two blocking calls.  4 = ungappedprefilter (prefilter's arguments; the exhaustive
+// gapless prefilter, ungappedprefilter.cpp); `search --prefilter-mode 1` runs it in place of the k-mer prefilter and then the alignment stage
+// (Search.cpp:323-350), two blocking calls as well.
+// Without a sequence lookup the gapless prefilter maps the target letters itself and turns lower-case letters (and the characters 32 to 52) into X
+// (ungappedprefilter.cpp:393-397); the alignment stage behind it reads the letters as always.  A database with such letters is therefore
+// given to the stage as a second, residues-only database with the same target order.
+int ungappedStage(const mk::Database &tdb, mk_targetdb *T, const std::vector<uint32_t> &keys, mk_queries *Q, const mk_params &P) {
+    bool masked = false;
+    for (size_t i = 0; i < tdb.entries.size() && !masked; i++) {
+        const char *s = tdb.entry(i);
+        for (size_t k = 0; k < tdb.seqLen(i); k++) if ((s[k] >= 32 && s[k] <= 52) || s[k] >= 97) { masked = true; break; }
+    }
+    if (!masked) return mk_ungapped_prefilter(T, Q, &P) == MK_OK ? 0 : die("%s", mk_last_error());
+    std::vector<uint8_t> res;
+    std::vector<uint64_t> off;
+    encodeDb(tdb, res, off);
+    for (size_t i = 0; i < tdb.entries.size(); i++) {
+        const char *s = tdb.entry(i);
+        for (size_t k = 0; k < tdb.seqLen(i); k++) if ((s[k] >= 32 && s[k] <= 52) || s[k] >= 97) res[off[i] + k] = 20;
+    }
+    mk_targetdb *X = nullptr;
+    if (mk_targetdb_create_sequences(res.data(), off.data(), (uint32_t) tdb.entries.size(), &P, &X) != MK_OK) return die("%s", mk_last_error());
+    if (mk_targetdb_set_keys(X, keys.data(), (uint32_t) keys.size()) != MK_OK || mk_ungapped_prefilter(X, Q, &P) != MK_OK) { mk_targetdb_destroy(X); return die("%s", mk_last_error()); }
+    mk_targetdb_destroy(X);
+    return 0;
+}
+
 int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
+    const bool isUngappedPref = mode == 4;
+    if (isUngappedPref) mode = 0;                                 // prefilter's arguments and output
     const bool isAlign = mode != 0, isSearch = mode == 2, isRescore = mode == 3;
     Args a;
-    if (int rc = parse(argc, argv, a, mode == 1 || mode == 2)) return rc;
+    if (int rc = parse(argc, argv, a, mode == 1 || mode == 2, isSearch)) return rc;
     const size_t need = isAlign ? 4 : 3;
     if (a.pos.size() != need) {
-        fprintf(stderr, "usage: metaeuk-amd %s <i:queryDB> <i:targetDB> %s[options]\n", isSearch ? "search" : (isRescore ? "rescorediagonal" : (isAlign ? "align" : "prefilter")),
+        fprintf(stderr, "usage: metaeuk-amd %s <i:queryDB> <i:targetDB> %s[options]\n", isSearch ? "search" : (isRescore ? "rescorediagonal" : (isAlign ? "align" : (isUngappedPref ? "ungappedprefilter" : "prefilter"))),
                 isSearch ? "<o:alignmentDB> <tmpDir> " : (isAlign ? "<i:resultDB> <o:alignmentDB> " : "<o:prefilterDB> "));
         return EXIT_FAILURE;
     }
@@ -681,6 +712,20 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         return die("%s needs --alignment-mode 2 or 3 (the module default, 0 = score only, is not implemented)", isSearch ? "search" : "align");
     // the ungapped stage: `rescorediagonal --rescore-mode 2`, or `search --alignment-mode 4` (the mode is no value of mk_params: `align` and
     // `predictexons` keep refusing it)
+    // --prefilter-mode (search): 0 = the k-mer prefilter, 1 = the gapless one; 2 (exhaustive alignment) and 3 (gapless, then gapped) are not built
+    bool ungPref = isUngappedPref;
+    if (a.opt.count("--prefilter-mode")) {
+        const std::string &v = a.opt["--prefilter-mode"];
+        if (v == "1") ungPref = true;
+        else if (v == "2" || v == "3") return die("--prefilter-mode %s: only 0 (k-mer prefilter) and 1 (ungapped prefilter) are implemented", v);
+        else if (v != "0") return die("--prefilter-mode %s: prefilter modes 0 to 3 exist", v);
+    }
+    if (ungPref) {
+        if (a.opt.count("--split") && atoi(a.opt["--split"].c_str()) > 1) return die("--split %s with the ungapped prefilter (--prefilter-mode 1) is not implemented: it searches the whole target DB", a.opt["--split"]);
+        char r0[PATH_MAX], r1[PATH_MAX];
+        const std::string p0 = realpath(a.pos[0].c_str(), r0) ? r0 : a.pos[0], p1 = realpath(a.pos[1].c_str(), r1) ? r1 : a.pos[1];
+        if (p0 == p1) return die("the ungapped prefilter with the query DB as the target DB (the identity rule of ungappedprefilter.cpp:388) is not implemented%s");
+    }
     bool ungapped = isRescore;
     if (isSearch && a.opt["--alignment-mode"] == "4") { ungapped = true; a.opt["--alignment-mode"] = "2"; }
     if (isRescore) {
@@ -728,6 +773,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     if (profileQueries && isSearch) return die("search with a profile query DB is not a workflow of the reference: use predictexons with a profile target DB, or prefilter / align / swapresults%s");
     if (profileQueries && ungapped) return die("the ungapped alignment stage does not take profile queries (the reference refuses them, Search.cpp:262-266)%s");
     if (profileQueries && altAli > 0) return die("--alt-ali with a profile query database is not implemented%s");
+    if (profileQueries && ungPref) return die("the ungapped prefilter (--prefilter-mode 1) with a profile query database is not implemented%s");
     if (profileQueries) { if (int rc = refuseFiltersForProfiles(P)) return rc; P.profile_search = 1; }
     Shard sh;
     if (int rc = shardOf(a, sh, argc, argv)) return rc;
@@ -753,6 +799,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         int32_t t = -1;
         if (f) { if (fread(&t, 4, 1, f) != 1) t = -1; fclose(f); }
         if (t >= 0 && (t & 0xFFFF) == DBTYPE_HMM_PROFILE) {
+            if (ungPref) return die("the ungapped prefilter (--prefilter-mode 1) with a profile target database is not implemented%s");
             if (ungapped) return die("the ungapped alignment stage does not take a profile target database (the reference refuses it, Search.cpp:262-266)%s");
             if (altAli > 0) return die("--alt-ali with a profile target database is not implemented%s");
             if (!isSearch || profileQueries) return die("a profile target database is searched by `search` / `predictexons` (the inverted sliced search), not by %s", isAlign ? "align" : "prefilter");
@@ -786,13 +833,15 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         int32_t t = -1;
         if (f) { if (fread(&t, 4, 1, f) != 1) t = -1; fclose(f); }
         const bool explicitSplit = a.opt.count("--split") && atoi(a.opt["--split"].c_str()) > 1 && a.opt.count("--split-mode") && a.opt["--split-mode"] == "0";
+        if (ungPref && t >= 0 && (t & 0xFFFF) == 9)
+            return die("the ungapped prefilter (--prefilter-mode 1) against an index DB is not implemented (its sequence lookup is the masked one): pass the sequence DB%s");
         const bool hasIdx = (t >= 0 && (t & 0xFFFF) == 9) || (!P.profile_search && !launcherEnv("MMSEQS_IGNORE_INDEX") && mk::Database::exists(a.pos[1] + ".idx.dbtype"));
         if (explicitSplit && t >= 0 && (t & 0xFFFF) == 9) return die("--split with --split-mode 0 needs an amino-acid sequence DB as the target (index DBs hold one split)%s");
-        if (t >= 0 && (t & 0xFFFF) == mk::DBTYPE_AMINO_ACIDS && (isAlign && !isSearch ? true : (explicitSplit || !hasIdx))) {
+        if (t >= 0 && (t & 0xFFFF) == mk::DBTYPE_AMINO_ACIDS && (isAlign && !isSearch ? true : (ungPref || explicitSplit || !hasIdx))) {
             e = tdbSeq.open(a.pos[1]);
             if (!e.empty()) return die("%s", e);
             haveSeqDb = true;
-            if (!isAlign || isSearch) {
+            if ((!isAlign || isSearch) && !ungPref) {
                 uint64_t aaSize = 0;
                 for (size_t i = 0; i < tdbSeq.entries.size(); i++) aaSize += tdbSeq.seqLen(i);
                 if (!profileQueries) { if (int rc = planTargetSplits(a, P, tdbSeq.entries.size(), aaSize, qdb.entries.size(), plan)) return rc; }
@@ -800,7 +849,9 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         }
     }
     const int targetSplits = plan.splits;
-    if (isAlign && !isSearch && haveSeqDb) { if (int rc = openTargetSequences(tdbSeq, P, ts)) return rc; }      // align: residues only, no index is built
+    if (ungPref && !haveSeqDb) return die("the ungapped prefilter (--prefilter-mode 1) needs an amino-acid sequence DB as the target, got %s", a.pos[1]);
+    if (ungPref) { if (int rc = openTargetSequences(tdbSeq, P, ts)) return rc; }                                // residues only: the mode needs no k-mer index
+    else if (isAlign && !isSearch && haveSeqDb) { if (int rc = openTargetSequences(tdbSeq, P, ts)) return rc; }      // align: residues only, no index is built
     else if (targetSplits == 1) { if (int rc = haveSeqDb ? openTargetDb(tdbSeq, P, ts) : openTarget(a.pos[1], P, ts)) return rc; }
     else if (isSearch) { if (int rc = openTargetSequences(tdbSeq, P, ts)) return rc; }                          // the alignment half of a split search
     mk_targetdb *T = ts.T;
@@ -830,7 +881,8 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         fprintf(stderr, "prefilter: %zu queries x %zu targets in %d target splits%s (--max-seqs %d per split, k = %d), %llu hits, %.2f s\n", nq, tdbSeq.entries.size(), targetSplits,
                 plan.chosen ? " [chosen from the memory limit]" : "", plan.maxSeqs, plan.kmerSize, (unsigned long long) total, now() - t0);
     } else if (!isAlign) {
-        if (mk_prefilter(T, Q, &P) != MK_OK) return die("%s", mk_last_error());
+        if (ungPref) { if (int rc = ungappedStage(tdbSeq, T, tkeys, Q, P)) return rc; }
+        else if (mk_prefilter(T, Q, &P) != MK_OK) return die("%s", mk_last_error());
         const mk_hit *hits; const uint64_t *hoff;
         mk_prefilter_result(Q, &hits, &hoff);
         mk::DatabaseWriter w(outPath, mk::DBTYPE_PREFILTER_RES);
@@ -844,8 +896,12 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         }
         e = w.close();
         if (!e.empty()) return die("%s", e);
-        printPrefilterStatistics(Q, P);
-        fprintf(stderr, "prefilter: %zu queries x %zu targets%s, %llu hits, %.2f s\n", nq, tkeys.size(), ts.fromIndex ? " (precomputed index)" : "", (unsigned long long) hoff[nq], now() - t0);
+        // (the k-mer statistics -- k-mers per position, DB matches, overflows -- belong to the k-mer prefilter: the gapless one has none to print)
+        if (ungPref) fprintf(stderr, "ungappedprefilter: %zu queries x %zu targets, every pair scored, %llu hits, %.2f s\n", nq, tkeys.size(), (unsigned long long) hoff[nq], now() - t0);
+        else {
+            printPrefilterStatistics(Q, P);
+            fprintf(stderr, "prefilter: %zu queries x %zu targets%s, %llu hits, %.2f s\n", nq, tkeys.size(), ts.fromIndex ? " (precomputed index)" : "", (unsigned long long) hoff[nq], now() - t0);
+        }
     } else {
         std::vector<mk_hit> hits;
         if (isSearch && targetSplits > 1) {
@@ -855,6 +911,12 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
             if ((ungapped ? mk_rescore_diagonal(T, Q, &P, 2, sortResults) : mk_align(T, Q, &P)) != MK_OK) return die("%s", mk_last_error());
             hits.resize(total);
             fprintf(stderr, "search: %d target splits%s (--max-seqs %d per split, k = %d)\n", targetSplits, plan.chosen ? " [chosen from the memory limit]" : "", plan.maxSeqs, plan.kmerSize);
+        } else if (isSearch && ungPref) {                          // ungappedprefilter, then align (or the ungapped alignment stage): two blocking calls
+            if (int rc = ungappedStage(tdbSeq, T, tkeys, Q, P)) return rc;
+            if ((ungapped ? mk_rescore_diagonal(T, Q, &P, 2, sortResults) : mk_align(T, Q, &P)) != MK_OK) return die("%s", mk_last_error());
+            const mk_hit *hp; const uint64_t *ho;
+            mk_prefilter_result(Q, &hp, &ho);
+            hits.resize(ho[nq]);
         } else if (isSearch) {
             if (ungapped) {                                          // prefilter, then rescorediagonal --rescore-mode 2: two blocking calls
                 if (mk_prefilter(T, Q, &P) != MK_OK || mk_rescore_diagonal(T, Q, &P, 2, sortResults) != MK_OK) return die("%s", mk_last_error());
@@ -1650,7 +1712,7 @@ int cmdCreateIndex(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "metaeuk-amd: MI355X prefilter+align modules of `metaeuk predictexons`\n  metaeuk-amd prefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd align <queryDB> <targetDB> <prefilterDB> <alignmentDB> [flags]\n  metaeuk-amd rescorediagonal <queryDB> <targetDB> <prefilterDB> <alignmentDB> --rescore-mode 2 [flags]\n  metaeuk-amd search <queryDB> <targetDB> <alignmentDB> <tmpDir> [flags]\n  metaeuk-amd extractorfs <contigDB> <orfDB> [--min-length N] [--translate 0|1] [--aa-sibling NAME]\n  metaeuk-amd predictexons <contigsDB> <targetsDB> <calledExonsDB> <tmpDir> [flags]\n  metaeuk-amd createindex <targetsDB> <tmpDir> [-s 7.5]\n");
+        fprintf(stderr, "metaeuk-amd: MI355X prefilter+align modules of `metaeuk predictexons`\n  metaeuk-amd prefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd align <queryDB> <targetDB> <prefilterDB> <alignmentDB> [flags]\n  metaeuk-amd rescorediagonal <queryDB> <targetDB> <prefilterDB> <alignmentDB> --rescore-mode 2 [flags]\n  metaeuk-amd ungappedprefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd search <queryDB> <targetDB> <alignmentDB> <tmpDir> [--prefilter-mode 0|1] [flags]\n  metaeuk-amd extractorfs <contigDB> <orfDB> [--min-length N] [--translate 0|1] [--aa-sibling NAME]\n  metaeuk-amd predictexons <contigsDB> <targetsDB> <calledExonsDB> <tmpDir> [flags]\n  metaeuk-amd createindex <targetsDB> <tmpDir> [-s 7.5]\n");
         return EXIT_FAILURE;
     }
     const std::string cmd = argv[1];
@@ -1658,6 +1720,7 @@ int main(int argc, char **argv) {
     if (cmd == "align") return cmdPrefilterOrAlign(1, argc, argv);
     if (cmd == "search") return cmdPrefilterOrAlign(2, argc, argv);
     if (cmd == "rescorediagonal") return cmdPrefilterOrAlign(3, argc, argv);
+    if (cmd == "ungappedprefilter") return cmdPrefilterOrAlign(4, argc, argv);
     if (cmd == "shardinfo" && argc >= 4) {                       // <db> r/N: the worker's entry range (first, count) -- for tests and scripts
         mk::Database db;
         const std::string e = db.open(argv[2]);
