@@ -314,6 +314,22 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *param
  * bias of the query's rows (NULL: none; what mk_queries_derived reports as sw_bias8).  q_len >= 1, t_len >= 0. */
 int mk_ungapped_prefilter_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int q_len, const uint8_t *t, int t_len, int *score);
 
+/* ---- gappedprefilter: the exhaustive Smith-Waterman score filter (M/src/prefiltering/ungappedprefilter.cpp:338-477 with alignmentMode 1:
+ * SmithWaterman::ssw_align with Matcher::SCORE_ONLY).  Every query is scored against every target with local Gotoh, gap open 11, gap extend 1,
+ * the alignment matrix plus the query's composition bias, the score capped at 32 767; only the score is computed.  A pair that fails
+ * Util::canBeCovered(cov_thr, cov_mode) is skipped; a hit is kept when score > min_ungapped_score (strictly) and, unless evalue_thr is DBL_MAX,
+ * its e-value (the database's evaluer with the gapped parameter set, as in mk_align) is at most evalue_thr; a query keeps its first max_seqs hits
+ * in hit_t::compareHitsByScoreAndId order (score descending, then the DB key ascending).  Fills the batch's PREFILTER result (seq_id = target
+ * index, pref_score = score, diagonal 0): mk_prefilter_result, mk_align, mk_rescore_diagonal and the formatters read it unchanged.  Works on
+ * mk_targetdb_create_sequences and mk_targetdb_create databases.  Honoured of params: max_seqs, min_ungapped_score, evalue_thr, comp_bias_corr,
+ * comp_bias_scale (the rule of mk_ungapped_prefilter: other values than the batch's are derived into scratch memory), cov_thr, cov_mode.
+ * Residue codes above 20 are read as X.  MK_ERR_UNSUPPORTED: profile queries or a profile database, a database opened from an index DB, a
+ * negative min_ungapped_score, gap costs other than 11 / 1. */
+int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *params);
+/* the score of ONE pair, host code without a GPU and without mk_init (the twin the kernel is checked against): the plain row loop in 32-bit
+ * integers.  Arguments as for mk_ungapped_prefilter_host. */
+int mk_gapped_prefilter_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int q_len, const uint8_t *t, int t_len, int *score);
+
 /* ---- --alt-ali N: alternative alignments (Alignment::computeAlternativeAlignment, M/src/alignment/Alignment.cpp:399-401, 569-601).  Runs after
  * mk_align / mk_search on the batch's alignment result and replaces it with the merged lists; mk_align_result and mk_format_alignment read it
  * unchanged.  Every accepted record is the origin of a chain: the target with [db_start, db_end) of the origin and of the chain's accepted

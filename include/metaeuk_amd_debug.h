@@ -39,6 +39,9 @@ uint64_t mk_debug_trace_left_band(const mk_queries *q);
  * profile image, lanes per target for short and for long targets, the target length from which the long shape is used.  The tests place their
  * edge cases with these, so a change of the header moves them */
 void mk_debug_ungapped_constants(int out[6]);
+/* the same for the gapped prefilter (metaeuk_amd/csrc/mk_gapped.hpp): lanes per target, queries per register, rows per lane of the three tile
+ * shapes (a tile is lanes x rows; the last shape walks longer queries in row tiles), blocks of 32 targets per work item */
+void mk_debug_gapped_constants(int out[6]);
 
 /* ---- experiment hook (tools/micro/mk_experiments.hip is its only user): the device view of a (database, batch) pair -- a
  * mk::PrefilterDeviceView (metaeuk_amd/csrc/mk_prefilter.hpp: pointers into HBM, valid while both handles live) copied into view_out, whose

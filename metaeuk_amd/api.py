@@ -56,7 +56,8 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_backtrace_host", "mk_sw_backtrace_pairs", "mk_align_backtrace", "mk_format_alignment_bt", "mk_format_alignments_bt", "mk_debug_trace_left_band",
            "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host", "mk_align_statistics", "mk_align_limit_scan",
            "mk_rescore_diagonal", "mk_rescore_diagonal_host", "mk_alt_alignments", "mk_alt_alignments_host",
-           "mk_ungapped_prefilter", "mk_ungapped_prefilter_host", "mk_debug_ungapped_constants"]
+           "mk_ungapped_prefilter", "mk_ungapped_prefilter_host", "mk_debug_ungapped_constants",
+           "mk_gapped_prefilter", "mk_gapped_prefilter_host", "mk_debug_gapped_constants"]
 
 
 def lib():
@@ -672,11 +673,16 @@ def rescore_diagonal_host(q, t, diagonal, db_residues, params, mat=None, rescore
 _UNG_NAMES = ("UNG_DIAGS", "UNG_PACK", "UNG_ROW_TILE", "UNG_GROUP_SHORT", "UNG_GROUP_LONG", "UNG_LONG_TARGET")
 
 
+# the gapped prefilter's: lanes per target, queries per register, rows per lane of the three tile shapes, target blocks per work item (csrc/mk_gapped.hpp)
+_GAP_NAMES = ("GAP_GROUP", "GAP_PACK", "GAP_ROWS_0", "GAP_ROWS_1", "GAP_ROWS_2", "GAP_BLOCKS_PER_WG")
+
+
 def __getattr__(name):
-    if name in _UNG_NAMES:
-        v = (C.c_int * 6)()
-        lib().mk_debug_ungapped_constants(v)
-        return int(v[_UNG_NAMES.index(name)])
+    for names, fn in ((_UNG_NAMES, "mk_debug_ungapped_constants"), (_GAP_NAMES, "mk_debug_gapped_constants")):
+        if name in names:
+            v = (C.c_int * 6)()
+            getattr(lib(), fn)(v)
+            return int(v[names.index(name)])
     raise AttributeError(name)
 
 
@@ -696,6 +702,25 @@ def ungapped_prefilter_host(q, t, q_bias8=None, mat=None):
     score = C.c_int()
     _chk(lib().mk_ungapped_prefilter_host(None if m is None else _p(m), _p(q), None if b is None else _p(b), C.c_int(len(q)), _p(tt), C.c_int(len(t)),
                                           C.byref(score)))
+    return int(score.value)
+
+
+def gapped_prefilter(db, q, params=None):
+    """gappedprefilter over the batch (mk_gapped_prefilter) -> (hits structured array [total], offsets uint64[n+1])"""
+    p = params or db.params
+    _chk(lib().mk_gapped_prefilter(db.h, q.h, C.byref(p)))
+    return prefilter_result(q)
+
+
+def gapped_prefilter_host(q, t, q_bias8=None, mat=None):
+    """the Smith-Waterman score of one pair of code arrays by the plain row loop, host code (mk_gapped_prefilter_host)"""
+    q = np.ascontiguousarray(q, dtype=np.uint8); t = np.ascontiguousarray(t, dtype=np.uint8)
+    b = None if q_bias8 is None else np.ascontiguousarray(q_bias8, dtype=np.int8)
+    m = None if mat is None else np.ascontiguousarray(mat, dtype=np.int8)
+    tt = t if len(t) else np.zeros(1, dtype=np.uint8)
+    score = C.c_int()
+    _chk(lib().mk_gapped_prefilter_host(None if m is None else _p(m), _p(q), None if b is None else _p(b), C.c_int(len(q)), _p(tt), C.c_int(len(t)),
+                                        C.byref(score)))
     return int(score.value)
 
 

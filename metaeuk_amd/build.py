@@ -8,8 +8,8 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", f) for f in ("mk_host.cpp", "mk_exons.cpp", "mk_indexfile.cpp", "mk_abi.cpp", "mk_sw.hip", "mk_align.hip", "mk_prefilter.hip", "mk_derive.hip", "mk_profile.hip", "mk_kmer7.hip", "mk_orf.hip", "mk_orf_host.cpp", "mk_index.hip", "mk_trace.hip", "mk_rescore.hip", "mk_altali.hip", "mk_ungapped.hip", "mk_synth.cpp", "mk_cli.cpp")]
-HDR = [os.path.join(HERE, "csrc", f) for f in ("mk_host.hpp", "mk_kernels.hpp", "mk_prefilter.hpp", "mk_align.hpp", "mk_dbio.hpp", "mk_enum.hpp", "mk_profile.hpp", "mk_kmer7.hpp", "mk_orf.hpp", "mk_orf_scan.hpp", "mk_exons.hpp", "mk_indexfile.hpp", "mk_index.hpp", "mk_segsort.hpp", "mk_filters.hpp", "mk_limits.hpp", "mk_trace.hpp", "mk_rescore.hpp", "mk_altali.hpp", "mk_ungapped.hpp")] + [
+SRC = [os.path.join(HERE, "csrc", f) for f in ("mk_host.cpp", "mk_exons.cpp", "mk_indexfile.cpp", "mk_abi.cpp", "mk_sw.hip", "mk_align.hip", "mk_prefilter.hip", "mk_derive.hip", "mk_profile.hip", "mk_kmer7.hip", "mk_orf.hip", "mk_orf_host.cpp", "mk_index.hip", "mk_trace.hip", "mk_rescore.hip", "mk_altali.hip", "mk_ungapped.hip", "mk_gapped.hip", "mk_synth.cpp", "mk_cli.cpp")]
+HDR = [os.path.join(HERE, "csrc", f) for f in ("mk_host.hpp", "mk_kernels.hpp", "mk_prefilter.hpp", "mk_align.hpp", "mk_dbio.hpp", "mk_enum.hpp", "mk_profile.hpp", "mk_kmer7.hpp", "mk_orf.hpp", "mk_orf_scan.hpp", "mk_exons.hpp", "mk_indexfile.hpp", "mk_index.hpp", "mk_segsort.hpp", "mk_filters.hpp", "mk_limits.hpp", "mk_trace.hpp", "mk_rescore.hpp", "mk_altali.hpp", "mk_ungapped.hpp", "mk_gapped.hpp")] + [
     os.path.join(HERE, "..", "include", "metaeuk_amd.h"), os.path.join(HERE, "..", "include", "metaeuk_amd_debug.h"), os.path.join(HERE, "data", "matrices.inc")]
 LIB = os.path.join(HERE, "lib", "libmetaeuk_amd.so")
 BIN = os.path.join(HERE, "lib", "metaeuk-amd")
@@ -19,9 +19,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fopenmp", "-ff
 # its records decide verdicts that must equal the host twin's bit for bit, and the unit stays free of v_pk_add / mul / fma_f32 whatever a later
 # compiler would choose.  hipcc hands the option to its host pass too, which prints "not a recognized feature" and ignores it.
 # mk_altali.hip: the same guard for the float expressions of its records.  mk_ungapped.hip: an integer kernel whose one float expression is the
-# length test of can_be_covered; it takes the guard with the other new units.
+# length test of can_be_covered; it takes the guard with the other new units, and so does mk_gapped.hip.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = {"mk_rescore.hip": NO_PK_F32, "mk_altali.hip": NO_PK_F32, "mk_ungapped.hip": NO_PK_F32}
+EXTRA = {"mk_rescore.hip": NO_PK_F32, "mk_altali.hip": NO_PK_F32, "mk_ungapped.hip": NO_PK_F32, "mk_gapped.hip": NO_PK_F32}
 
 
 def _stale(target, deps):

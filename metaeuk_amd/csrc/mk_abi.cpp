@@ -18,6 +18,7 @@
 #include "mk_rescore.hpp"
 #include "mk_trace.hpp"
 #include "mk_ungapped.hpp"
+#include "mk_gapped.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -2397,6 +2398,191 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
 // the kernel's work split as the tests read it (metaeuk_amd_debug.h)
 void mk_debug_ungapped_constants(int out[6]) {
     out[0] = mk::UNG_DIAGS; out[1] = mk::UNG_PACK; out[2] = mk::UNG_ROW_TILE; out[3] = mk::UNG_GROUP_SHORT; out[4] = mk::UNG_GROUP_LONG; out[5] = mk::UNG_LONG_TARGET;
+}
+
+// ---- gappedprefilter (mk_gapped.hpp / mk_gapped.hip) ---------------------------------------------------------------------------------
+int mk_gapped_prefilter_host(const int8_t *mat, const uint8_t *q, const int8_t *qBias8, int qLen, const uint8_t *t, int tLen, int *score) {
+    if (!q || !score || qLen <= 0 || tLen < 0 || (!t && tLen > 0)) return fail(MK_ERR_ARG, "mk_gapped_prefilter_host: null argument, empty query or negative length");
+    int8_t own[441];
+    if (!mat) {
+        mk::SubMat m;
+        mk::build_submat(m, mk::MAT_BLOSUM62, 2.0f, 0.0f);
+        for (int i = 0; i < 21; i++) for (int j = 0; j < 21; j++) own[i * 21 + j] = (int8_t) m.sub[i][j];
+        mat = own;
+    }
+    *score = mk::gapped_pair_host(mat, q, qBias8, qLen, t, tLen);
+    return MK_OK;
+}
+
+// the launches of one (query chunk, target chunk): the chunk's query pairs by tile shape (the queries are sorted by length, so a shape is a range
+// of pairs), and for the pairs beyond the largest tile the target ranges by length class, each with as many workgroups as its parked rows leave room for
+struct GappedParkLaunch { uint32_t a, b, stride, blocks; };
+static void gapped_park_plan(const std::vector<uint32_t> &lens, uint32_t s0, uint32_t ns, uint32_t pairs, std::vector<GappedParkLaunch> &out) {
+    out.clear();
+    uint32_t a = 0;
+    for (uint64_t limit = 512; a < ns; limit *= 4) {              // length classes 1 .. 512, .. 2048, .. 8192, ...: a strip is as long as its class's longest target
+        const uint32_t b = (uint32_t) (std::upper_bound(lens.begin() + s0 + a, lens.begin() + s0 + ns, (uint32_t) std::min<uint64_t>(limit, UINT32_MAX)) - (lens.begin() + s0));
+        if (b == a) continue;
+        GappedParkLaunch L;
+        L.a = a; L.b = b; L.stride = std::max<uint32_t>(lens[s0 + b - 1], 1);
+        const uint64_t perBlock = (uint64_t) mk::gapped_park_strips() * L.stride * sizeof(uint2);
+        const uint64_t items = (uint64_t) pairs * (((b - a + 31) / 32 + mk::GAP_BLOCKS_PER_WG - 1) / mk::GAP_BLOCKS_PER_WG);
+        L.blocks = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(mk::GAP_PARK_BUDGET / perBlock, 1), std::max<uint64_t>(items, 1));
+        out.push_back(L);
+        a = b;
+    }
+}
+
+int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
+    if (q->isProfile || db->profileSearch || P->profile_search != 0)
+        return fail(MK_ERR_UNSUPPORTED, "gappedprefilter with profile queries or a profile database is not implemented");
+    if (db->fromIndex)
+        return fail(MK_ERR_UNSUPPORTED, "gappedprefilter against an index DB is not implemented (its sequence lookup is the masked one): pass the sequence DB");
+    if ((rc = check_filters(P, false)) != MK_OK) return rc;
+    if (P->max_seqs < 1) return fail(MK_ERR_ARG, "--max-seqs %d: a positive number is expected", P->max_seqs);
+    if (P->min_ungapped_score < 0)
+        return fail(MK_ERR_UNSUPPORTED, "--min-ungapped-score %d: a negative threshold keeps pairs of score 0, which the score array does not tell from skipped pairs", P->min_ungapped_score);
+    if (P->gap_open != mk::GAP_OPEN || P->gap_extend != mk::GAP_EXTEND)
+        return fail(MK_ERR_UNSUPPORTED, "gappedprefilter with gap costs %d / %d: only %d / %d have a Gumbel parameter set in the reference", P->gap_open, P->gap_extend, mk::GAP_OPEN, mk::GAP_EXTEND);
+    const int8_t *bias8 = nullptr;
+    if ((rc = ungapped_comp_bias(q, P, &bias8)) != MK_OK) return rc;
+    if ((rc = ungapped_target_orders(db)) != MK_OK) return rc;                  // the orders of the target side are the gapless stage's
+    const uint32_t nq = q->n, nt = db->n, maxSeqs = (uint32_t) std::min<int64_t>(P->max_seqs, std::max<uint32_t>(nt, 1));
+    q->pfStats = mk::PrefilterStats();
+    q->hitOff.assign((size_t) nq + 1, 0);
+    q->nHits = 0;
+    if (nq == 0 || nt == 0) {
+        if (!q->hits.reserve(sizeof(mk_hit), 0)) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+        q->havePref = true;
+        return MK_OK;
+    }
+    // queries by ascending length: two neighbours share a register, and a tile shape is a range of pairs
+    std::vector<uint32_t> qOrder(nq);
+    for (uint32_t i = 0; i < nq; i++) qOrder[i] = i;
+    std::stable_sort(qOrder.begin(), qOrder.end(), [&](uint32_t a, uint32_t b) { return q->off[a + 1] - q->off[a] < q->off[b + 1] - q->off[b]; });
+    const auto qLenAt = [&](uint32_t pos) { return (uint32_t) (q->off[qOrder[pos] + 1] - q->off[qOrder[pos]]); };
+    // the e-value verdict per query length and score (the alignment stage's gate: the database's evaluer, gapped parameter set)
+    std::shared_ptr<const ScoreTabs> tabs;
+    mk::GateEntry *dGate = nullptr;
+    if (P->evalue_thr < std::numeric_limits<double>::max()) {
+        tabs = score_tables(db, q, P->evalue_thr);
+        dGate = (mk::GateEntry *) mk::dev_scratch("gapped_gate", tabs->gate.size() * sizeof(mk::GateEntry));
+        if (!dGate) return fail(MK_ERR_DEVICE, "device scratch allocation failed (gapped prefilter, gate)");
+        HIPCHK(hipMemcpyAsync(dGate, tabs->gate.data(), tabs->gate.size() * sizeof(mk::GateEntry), hipMemcpyHostToDevice, g_stream));
+    }
+    // the score array: [queries of the chunk][targets of the chunk] int16 within the budget (MK_GAPPED_SCORE_BUDGET, bytes, shrinks it for the tests)
+    uint64_t budget = mk::GAP_SCORE_BUDGET;
+    if (const char *k = mk::knob("MK_GAPPED_SCORE_BUDGET")) budget = strtoull(k, nullptr, 10);
+    const uint64_t room = std::max<uint64_t>(budget / sizeof(int16_t), mk::GAP_PACK);
+    const uint32_t nsC = (uint32_t) std::min<uint64_t>(nt, std::max<uint64_t>(1, room / mk::GAP_PACK));
+    uint64_t nqC64 = std::max<uint64_t>(mk::GAP_PACK, room / nsC / mk::GAP_PACK * mk::GAP_PACK);
+    nqC64 = std::min<uint64_t>(nqC64, std::max<uint64_t>(mk::GAP_PACK, ((16ull << 20) / maxSeqs) / mk::GAP_PACK * mk::GAP_PACK));     // (the hit block of a chunk)
+    const uint32_t nqC = (uint32_t) std::min<uint64_t>(std::min<uint64_t>(nqC64, 65535ull * mk::GAP_PACK), ((uint64_t) nq + mk::GAP_PACK - 1) / mk::GAP_PACK * mk::GAP_PACK);
+    // the parked rows of the queries beyond the largest tile: the most any launch of the call needs
+    std::vector<GappedParkLaunch> parkPlan;
+    uint64_t parkBytes = 0;
+    for (uint32_t q0 = 0; q0 < nq; q0 += nqC) {
+        const uint32_t n = std::min(nqC, nq - q0), pairs = (n + 1) / 2;
+        uint32_t longPairs = 0;
+        for (uint32_t p = 0; p < pairs; p++) longPairs += qLenAt(q0 + std::min(2 * p + 1, n - 1)) > (uint32_t) mk::GAP_MAX_TILE;
+        if (!longPairs) continue;
+        for (uint32_t s0 = 0; s0 < nt; s0 += nsC) {
+            gapped_park_plan(db->ungLens, s0, std::min(nsC, nt - s0), longPairs, parkPlan);
+            for (const GappedParkLaunch &L : parkPlan) parkBytes = std::max<uint64_t>(parkBytes, (uint64_t) L.blocks * mk::gapped_park_strips() * L.stride * sizeof(uint2));
+        }
+    }
+
+    uint32_t *dQOrder = (uint32_t *) mk::dev_scratch("gapped_qorder", (size_t) nq * 4);
+    int16_t *dScores = (int16_t *) mk::dev_scratch("gapped_scores", (size_t) nqC * nsC * sizeof(int16_t));
+    uint2 *dPark = parkBytes ? (uint2 *) mk::dev_scratch("gapped_park", parkBytes) : nullptr;
+    uint64_t *dCand = (uint64_t *) mk::dev_scratch("gapped_cand", (size_t) nqC * maxSeqs * 8), *dTmp = (uint64_t *) mk::dev_scratch("gapped_tmp", (size_t) nqC * maxSeqs * 8);
+    mk_hit *dHits = (mk_hit *) mk::dev_scratch("gapped_hits", (size_t) nqC * maxSeqs * sizeof(mk_hit));
+    uint32_t *dCnt = (uint32_t *) mk::dev_scratch("gapped_cnt", (size_t) nqC * 8 + 16), *dHitCnt = dCnt ? dCnt + nqC : nullptr;
+    unsigned long long *dWork = dCnt ? (unsigned long long *) (dCnt + 2 * (size_t) nqC) : nullptr;
+    mk_hit *hHits = (mk_hit *) mk::pinned_scratch("gapped_hits_h", (size_t) nqC * maxSeqs * sizeof(mk_hit));
+    uint32_t *hCnt = (uint32_t *) mk::pinned_scratch("gapped_cnt_h", (size_t) nqC * 4 + 16);
+    if (!dQOrder || !dScores || (parkBytes && !dPark) || !dCand || !dTmp || !dHits || !dCnt || !hHits || !hCnt) return fail(MK_ERR_DEVICE, "device scratch allocation failed (gapped prefilter)");
+    HIPCHK(hipMemcpyAsync(dQOrder, qOrder.data(), (size_t) nq * 4, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemsetAsync(dWork, 0, 16, g_stream));
+
+    mk::GappedView V;
+    V.q_res = q->dRes.p; V.q_off = q->dOff.p; V.q_bias8 = bias8; V.n_queries = nq; V.q_order = dQOrder;
+    V.t_res = db->dRes.p; V.t_off = db->dOff.p; V.n_targets = nt; V.t_order = db->dUngOrder.p;
+    V.mat = db->dMatAln.p;                       // [q * 21 + t]; the kernel reads [t * 21 + q]: the alignment matrix is symmetric
+    V.cov_thr = P->cov_thr; V.cov_mode = P->cov_mode;
+    V.scores = dScores; V.work = dWork; V.gate = dGate;
+    V.q0 = V.nq = V.s0 = V.ns = 0;
+    mk::GappedSelect S;
+    S.key_rank = db->dUngKeyRank.p; S.rank_idx = db->dUngRankIdx.p; S.min_score = P->min_ungapped_score; S.max_seqs = maxSeqs;
+    S.cand = dCand; S.cand_cnt = dCnt; S.tmp = dTmp; S.hits = dHits; S.hit_cnt = dHitCnt; S.last = false;
+
+    struct FlushTimers { ~FlushTimers() { timed_flush(); } } flushTimers;
+    HostTimer ht("host_gapped_prefilter_total");
+    std::vector<mk_hit> staged;                      // the chunks' lists in the order of qOrder
+    std::vector<uint32_t> cnt(nq, 0);
+    int lastScoreTimer = -1;                         // (the work counters run over the whole call: the last timer carries them, as in mk_ungapped_prefilter)
+    for (uint32_t q0 = 0; q0 < nq; q0 += nqC) {
+        V.q0 = q0; V.nq = std::min(nqC, nq - q0);
+        // the pair ranges of the shapes: [edge[k], edge[k + 1]) runs shape k, [edge[GAP_SHAPES], pairs) the last shape in row tiles
+        const uint32_t pairs = (V.nq + 1) / 2;
+        uint32_t edge[mk::GAP_SHAPES + 2] = {0};
+        for (int k = 0; k < mk::GAP_SHAPES; k++) {
+            uint32_t p = edge[k];
+            while (p < pairs && qLenAt(q0 + std::min(2 * p + 1, V.nq - 1)) <= (uint32_t) (mk::GAP_GROUP * mk::gapped_shape_rows(k))) p++;
+            edge[k + 1] = p;
+        }
+        edge[mk::GAP_SHAPES + 1] = pairs;
+        HIPCHK(hipMemsetAsync(dCnt, 0, (size_t) V.nq * 4, g_stream));
+        for (uint32_t s0 = 0; s0 < nt; s0 += nsC) {
+            V.s0 = s0; V.ns = std::min(nsC, nt - s0);
+            const int th = lastScoreTimer = timed_begin("gapped_prefilter", 0, 0);
+            for (int k = 0; k < mk::GAP_SHAPES; k++) HIPCHK(mk::launch_gapped_scores(V, k, edge[k], edge[k + 1], 0, V.ns, nullptr, 0, 0, g_stream));
+            if (edge[mk::GAP_SHAPES] < pairs) {
+                gapped_park_plan(db->ungLens, s0, V.ns, pairs - edge[mk::GAP_SHAPES], parkPlan);
+                for (const GappedParkLaunch &L : parkPlan)
+                    HIPCHK(mk::launch_gapped_scores(V, mk::GAP_SHAPES - 1, edge[mk::GAP_SHAPES], pairs, L.a, L.b, dPark, L.stride, L.blocks, g_stream));
+            }
+            timed_end(th);
+            S.last = s0 + V.ns == nt;
+            const int ts = timed_begin("gapped_select", (double) V.nq * V.ns * 7.0, 0);
+            HIPCHK(mk::launch_gapped_select(V, S, g_stream));
+            timed_end(ts);
+        }
+        HIPCHK(hipMemcpyAsync(hCnt, dHitCnt, (size_t) V.nq * 4, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hHits, dHits, (size_t) V.nq * maxSeqs * sizeof(mk_hit), hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        for (uint32_t r = 0; r < V.nq; r++) {
+            if (hCnt[r] > maxSeqs) return fail(MK_ERR_DEVICE, "gapped prefilter: a list of %u hits (at most %u)", hCnt[r], maxSeqs);
+            cnt[qOrder[q0 + r]] = hCnt[r];
+            staged.insert(staged.end(), hHits + (size_t) r * maxSeqs, hHits + (size_t) r * maxSeqs + hCnt[r]);
+        }
+    }
+    HIPCHK(hipMemcpyAsync(hCnt, dWork, 16, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    unsigned long long work[2];
+    std::memcpy(work, hCnt, 16);
+    timed_set(lastScoreTimer, (double) work[0], (double) work[1]);
+    for (uint32_t i = 0; i < nq; i++) q->hitOff[i + 1] = q->hitOff[i] + cnt[i];
+    q->nHits = q->hitOff[nq];
+    if (!q->hits.reserve(std::max<size_t>(q->nHits, 1) * sizeof(mk_hit), 0)) return fail(MK_ERR_DEVICE, "pinned host allocation failed");
+    size_t at = 0;
+    for (uint32_t r = 0; r < nq; r++) {                  // staged list r belongs to query qOrder[r]
+        const uint32_t qi = qOrder[r];
+        if (cnt[qi]) std::memcpy((mk_hit *) q->hits.p + q->hitOff[qi], staged.data() + at, (size_t) cnt[qi] * sizeof(mk_hit));
+        at += cnt[qi];
+    }
+    q->havePref = true;
+    return MK_OK;
+}
+
+// the kernel's work split as the tests read it (metaeuk_amd_debug.h)
+void mk_debug_gapped_constants(int out[6]) {
+    out[0] = mk::GAP_GROUP; out[1] = mk::GAP_PACK;
+    for (int k = 0; k < mk::GAP_SHAPES; k++) out[2 + k] = mk::gapped_shape_rows(k);
+    out[5] = mk::GAP_BLOCKS_PER_WG;
 }
 
 // ---- --alt-ali (mk_altali.hpp / mk_altali.hip) --------------------------------------------------------------------------------------

@@ -665,17 +665,19 @@ int openTargetSequences(const mk::Database &tdb, const mk_params &P, TargetSide 
 // ungapped alignment of every hit on its diagonal, rescorediagonal.cpp).  `search --alignment-mode 4` runs the prefilter and then the stage of
 // mode 3 with rescore mode 2 (Search.cpp:261, 314-315, 387), two blocking calls.  4 = ungappedprefilter (prefilter's arguments; the exhaustive
 // gapless prefilter, ungappedprefilter.cpp); `search --prefilter-mode 1` runs it in place of the k-mer prefilter and then the alignment stage
-// (Search.cpp:323-350), two blocking calls as well.
+// (Search.cpp:323-350), two blocking calls as well.  5 = gappedprefilter (the same module with alignmentMode 1: every pair scored by Smith-Waterman and
+// gated by the e-value, mk_gapped_prefilter); it shares the arguments, the refused corners and the lower-case rule of mode 4.
 // Without a sequence lookup the gapless prefilter maps the target letters itself and turns lower-case letters (and the characters 32 to 52) into X
 // (ungappedprefilter.cpp:393-397); the alignment stage behind it reads the letters as always.  A database with such letters is therefore
 // given to the stage as a second, residues-only database with the same target order.
-int ungappedStage(const mk::Database &tdb, mk_targetdb *T, const std::vector<uint32_t> &keys, mk_queries *Q, const mk_params &P) {
+int ungappedStage(const mk::Database &tdb, mk_targetdb *T, const std::vector<uint32_t> &keys, mk_queries *Q, const mk_params &P, bool gapped = false) {
+    const auto stage = gapped ? mk_gapped_prefilter : mk_ungapped_prefilter;
     bool masked = false;
     for (size_t i = 0; i < tdb.entries.size() && !masked; i++) {
         const char *s = tdb.entry(i);
         for (size_t k = 0; k < tdb.seqLen(i); k++) if ((s[k] >= 32 && s[k] <= 52) || s[k] >= 97) { masked = true; break; }
     }
-    if (!masked) return mk_ungapped_prefilter(T, Q, &P) == MK_OK ? 0 : die("%s", mk_last_error());
+    if (!masked) return stage(T, Q, &P) == MK_OK ? 0 : die("%s", mk_last_error());
     std::vector<uint8_t> res;
     std::vector<uint64_t> off;
     encodeDb(tdb, res, off);
@@ -685,27 +687,27 @@ int ungappedStage(const mk::Database &tdb, mk_targetdb *T, const std::vector<uin
     }
     mk_targetdb *X = nullptr;
     if (mk_targetdb_create_sequences(res.data(), off.data(), (uint32_t) tdb.entries.size(), &P, &X) != MK_OK) return die("%s", mk_last_error());
-    if (mk_targetdb_set_keys(X, keys.data(), (uint32_t) keys.size()) != MK_OK || mk_ungapped_prefilter(X, Q, &P) != MK_OK) { mk_targetdb_destroy(X); return die("%s", mk_last_error()); }
+    if (mk_targetdb_set_keys(X, keys.data(), (uint32_t) keys.size()) != MK_OK || stage(X, Q, &P) != MK_OK) { mk_targetdb_destroy(X); return die("%s", mk_last_error()); }
     mk_targetdb_destroy(X);
     return 0;
 }
 
 int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
-    const bool isUngappedPref = mode == 4;
+    const bool isGappedPref = mode == 5, isUngappedPref = mode == 4 || isGappedPref;
     if (isUngappedPref) mode = 0;                                 // prefilter's arguments and output
     const bool isAlign = mode != 0, isSearch = mode == 2, isRescore = mode == 3;
     Args a;
     if (int rc = parse(argc, argv, a, mode == 1 || mode == 2, isSearch)) return rc;
     const size_t need = isAlign ? 4 : 3;
     if (a.pos.size() != need) {
-        fprintf(stderr, "usage: metaeuk-amd %s <i:queryDB> <i:targetDB> %s[options]\n", isSearch ? "search" : (isRescore ? "rescorediagonal" : (isAlign ? "align" : (isUngappedPref ? "ungappedprefilter" : "prefilter"))),
+        fprintf(stderr, "usage: metaeuk-amd %s <i:queryDB> <i:targetDB> %s[options]\n", isSearch ? "search" : (isRescore ? "rescorediagonal" : (isAlign ? "align" : (isGappedPref ? "gappedprefilter" : (isUngappedPref ? "ungappedprefilter" : "prefilter")))),
                 isSearch ? "<o:alignmentDB> <tmpDir> " : (isAlign ? "<i:resultDB> <o:alignmentDB> " : "<o:prefilterDB> "));
         return EXIT_FAILURE;
     }
     mk_params P;
     int gpu = 0;
     if (isSearch && a.opt.find("-s") == a.opt.end()) a.opt["-s"] = "5.7";   // the search workflow's own default (Search.cpp:24)
-    if (isAlign && a.opt.find("-e") == a.opt.end()) a.opt["-e"] = "0.001"; // Parameters.cpp:2414 (predictexons passes -e 100 explicitly)
+    if ((isAlign || isGappedPref) && a.opt.find("-e") == a.opt.end()) a.opt["-e"] = "0.001"; // Parameters.cpp:2414 (predictexons passes -e 100 explicitly)
     // the module's own default --alignment-mode 0 resolves to score-only output (Alignment.cpp:168-178), which is not built:
     // the caller has to ask for mode 2, as predictexons does (PredictExons.cpp:13)
     if (isAlign && !isRescore && a.opt.find("--alignment-mode") == a.opt.end())
@@ -721,10 +723,11 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         else if (v != "0") return die("--prefilter-mode %s: prefilter modes 0 to 3 exist", v);
     }
     if (ungPref) {
-        if (a.opt.count("--split") && atoi(a.opt["--split"].c_str()) > 1) return die("--split %s with the ungapped prefilter (--prefilter-mode 1) is not implemented: it searches the whole target DB", a.opt["--split"]);
+        if (a.opt.count("--split") && atoi(a.opt["--split"].c_str()) > 1) return die(isGappedPref ? "--split %s with gappedprefilter is not implemented: it searches the whole target DB" : "--split %s with the ungapped prefilter (--prefilter-mode 1) is not implemented: it searches the whole target DB", a.opt["--split"]);
         char r0[PATH_MAX], r1[PATH_MAX];
         const std::string p0 = realpath(a.pos[0].c_str(), r0) ? r0 : a.pos[0], p1 = realpath(a.pos[1].c_str(), r1) ? r1 : a.pos[1];
-        if (p0 == p1) return die("the ungapped prefilter with the query DB as the target DB (the identity rule of ungappedprefilter.cpp:388) is not implemented%s");
+        if (p0 == p1) return die(isGappedPref ? "gappedprefilter with the query DB as the target DB (the identity rule of ungappedprefilter.cpp:388) is not implemented%s"
+                                              : "the ungapped prefilter with the query DB as the target DB (the identity rule of ungappedprefilter.cpp:388) is not implemented%s");
     }
     bool ungapped = isRescore;
     if (isSearch && a.opt["--alignment-mode"] == "4") { ungapped = true; a.opt["--alignment-mode"] = "2"; }
@@ -881,7 +884,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         fprintf(stderr, "prefilter: %zu queries x %zu targets in %d target splits%s (--max-seqs %d per split, k = %d), %llu hits, %.2f s\n", nq, tdbSeq.entries.size(), targetSplits,
                 plan.chosen ? " [chosen from the memory limit]" : "", plan.maxSeqs, plan.kmerSize, (unsigned long long) total, now() - t0);
     } else if (!isAlign) {
-        if (ungPref) { if (int rc = ungappedStage(tdbSeq, T, tkeys, Q, P)) return rc; }
+        if (ungPref) { if (int rc = ungappedStage(tdbSeq, T, tkeys, Q, P, isGappedPref)) return rc; }
         else if (mk_prefilter(T, Q, &P) != MK_OK) return die("%s", mk_last_error());
         const mk_hit *hits; const uint64_t *hoff;
         mk_prefilter_result(Q, &hits, &hoff);
@@ -897,7 +900,7 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
         e = w.close();
         if (!e.empty()) return die("%s", e);
         // (the k-mer statistics -- k-mers per position, DB matches, overflows -- belong to the k-mer prefilter: the gapless one has none to print)
-        if (ungPref) fprintf(stderr, "ungappedprefilter: %zu queries x %zu targets, every pair scored, %llu hits, %.2f s\n", nq, tkeys.size(), (unsigned long long) hoff[nq], now() - t0);
+        if (ungPref) fprintf(stderr, "%s: %zu queries x %zu targets, every pair scored, %llu hits, %.2f s\n", isGappedPref ? "gappedprefilter" : "ungappedprefilter", nq, tkeys.size(), (unsigned long long) hoff[nq], now() - t0);
         else {
             printPrefilterStatistics(Q, P);
             fprintf(stderr, "prefilter: %zu queries x %zu targets%s, %llu hits, %.2f s\n", nq, tkeys.size(), ts.fromIndex ? " (precomputed index)" : "", (unsigned long long) hoff[nq], now() - t0);
@@ -1712,7 +1715,7 @@ int cmdCreateIndex(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "metaeuk-amd: MI355X prefilter+align modules of `metaeuk predictexons`\n  metaeuk-amd prefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd align <queryDB> <targetDB> <prefilterDB> <alignmentDB> [flags]\n  metaeuk-amd rescorediagonal <queryDB> <targetDB> <prefilterDB> <alignmentDB> --rescore-mode 2 [flags]\n  metaeuk-amd ungappedprefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd search <queryDB> <targetDB> <alignmentDB> <tmpDir> [--prefilter-mode 0|1] [flags]\n  metaeuk-amd extractorfs <contigDB> <orfDB> [--min-length N] [--translate 0|1] [--aa-sibling NAME]\n  metaeuk-amd predictexons <contigsDB> <targetsDB> <calledExonsDB> <tmpDir> [flags]\n  metaeuk-amd createindex <targetsDB> <tmpDir> [-s 7.5]\n");
+        fprintf(stderr, "metaeuk-amd: MI355X prefilter+align modules of `metaeuk predictexons`\n  metaeuk-amd prefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd align <queryDB> <targetDB> <prefilterDB> <alignmentDB> [flags]\n  metaeuk-amd rescorediagonal <queryDB> <targetDB> <prefilterDB> <alignmentDB> --rescore-mode 2 [flags]\n  metaeuk-amd ungappedprefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd gappedprefilter <queryDB> <targetDB> <prefilterDB> [flags]\n  metaeuk-amd search <queryDB> <targetDB> <alignmentDB> <tmpDir> [--prefilter-mode 0|1] [flags]\n  metaeuk-amd extractorfs <contigDB> <orfDB> [--min-length N] [--translate 0|1] [--aa-sibling NAME]\n  metaeuk-amd predictexons <contigsDB> <targetsDB> <calledExonsDB> <tmpDir> [flags]\n  metaeuk-amd createindex <targetsDB> <tmpDir> [-s 7.5]\n");
         return EXIT_FAILURE;
     }
     const std::string cmd = argv[1];
@@ -1721,6 +1724,7 @@ int main(int argc, char **argv) {
     if (cmd == "search") return cmdPrefilterOrAlign(2, argc, argv);
     if (cmd == "rescorediagonal") return cmdPrefilterOrAlign(3, argc, argv);
     if (cmd == "ungappedprefilter") return cmdPrefilterOrAlign(4, argc, argv);
+    if (cmd == "gappedprefilter") return cmdPrefilterOrAlign(5, argc, argv);
     if (cmd == "shardinfo" && argc >= 4) {                       // <db> r/N: the worker's entry range (first, count) -- for tests and scripts
         mk::Database db;
         const std::string e = db.open(argv[2]);

@@ -2,6 +2,7 @@
 # VGPRs / SGPRs / LDS / scratch of every gfx950 kernel in an object file of the product (metaeuk_amd/lib/obj/*.o) or of the experiment library:
 #   tools/kernel_resources.sh metaeuk_amd/lib/obj/mk_sw.hip.o [name filter]
 #   tools/kernel_resources.sh metaeuk_amd/lib/obj/mk_ungapped.hip.o        (the gapless prefilter: registers, LDS, spills; it has no scratch)
+#   tools/kernel_resources.sh metaeuk_amd/lib/obj/mk_gapped.hip.o          (the gapped prefilter: one score kernel per tile shape, the selection)
 set -e
 OBJ=$1; FILTER=${2:-.}
 T=$(mktemp -d)
