@@ -7,7 +7,7 @@
 //   * int8 SW composition bias: SmithWaterman::ssw_init (M/src/alignment/StripedSmithWaterman.cpp:1228-1235).
 // The float/double expression types of the reference are kept literally; the build uses -ffp-contract=off, the
 // f64 division of gfx950 is correctly rounded, so every value is bit-identical to the host expressions
-// (tests/test_gpu_parity.py::test_device_derive_matches_host compares all four arrays).
+// (tests/test_gpu_parity.py::test_device_derive_matches_oracle compares all four arrays).
 #include "mk_kernels.hpp"
 #include "mk_host.hpp"
 

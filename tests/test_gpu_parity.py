@@ -130,6 +130,8 @@ def test_full_dp_position_passes_equal_the_early_exit(gpu_api, monkeypatch):
 
 
 def test_ungapped(gpu_api, small_workload):
+    """mk_ungapped: ungapped_kernel of mk_sw.hip and the generic per-byte ungapped_score on random (query, target, diagonal) triples -- NOT
+    diag_score_kernel, whose dword scorer (ungapped_score_dwords) is met through the prefilter only: tests/test_gpu_pf_cases.py, group S"""
     import ctypes as C
     targets, queries = small_workload
     api = gpu_api
