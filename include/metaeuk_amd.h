@@ -306,13 +306,22 @@ int mk_rescore_diagonal_host(const int8_t *mat21x21, const uint8_t *q, int q_len
  * the values the batch was created with, the call derives the composition bias it scores with into scratch memory of its own; the batch, and what
  * every other stage reads from it, stays as mk_queries_create made it.  Precondition: residue codes 0 .. 20 on both sides, as mk_encode yields
  * them (the kernel looks a target code up modulo 32 and keeps code 31 for window positions outside the target; the twin reads every code above
- * 20 as X -- larger codes are scored differently by the two).  MK_ERR_UNSUPPORTED: profile queries or a profile
- * database, a database opened from an index DB (its lookup is the masked one), a negative min_ungapped_score. */
+ * 20 as X -- larger codes are scored differently by the two).
+ * Profile queries (the inverted search of a profile target database: the profiles are the queries, the fragments the targets, mk_swap_alignments
+ * turns the aligned lists round) are taken in exactly the roles mk_search asks for: a batch of mk_profiles_create, a database created with
+ * params->profile_search = 1 and a call with params->profile_search = 1.  The score is then the same recurrence over the batch's int8 alignment
+ * profile (aln32 of mk_profiles_derived): X, and every target code above 20, scores 0 in every column, bias = |min(0, the 20 amino-acid scores of
+ * all columns)|, and there is no composition bias (comp_bias_corr / comp_bias_scale have no effect).  Verdicts, order, cut and result are the same.
+ * MK_ERR_UNSUPPORTED: a profile batch, a profile_search database or params->profile_search = 1 in any other combination, a database opened from an
+ * index DB (its lookup is the masked one), a negative min_ungapped_score. */
 int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *params);
 /* the score of ONE pair, host code without a GPU and without mk_init (the twin the kernel is checked against): cell by cell in the literal
  * unsigned-byte steps.  mat21x21 = int8 scores [t * 21 + q] (NULL: the alignment matrix), q / t = residue codes, q_bias8 = the int8 composition
  * bias of the query's rows (NULL: none; what mk_queries_derived reports as sw_bias8).  q_len >= 1, t_len >= 0. */
 int mk_ungapped_prefilter_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int q_len, const uint8_t *t, int t_len, int *score);
+/* the same for ONE (profile, target) pair: aln32 = the [n_cols][32] int8 alignment profile as mk_profiles_derived reports it (entries 0 .. 19 are
+ * read), t = residue codes.  n_cols >= 1, t_len >= 0. */
+int mk_ungapped_prefilter_profile_host(const int8_t *aln32, int n_cols, const uint8_t *t, int t_len, int *score);
 
 /* ---- gappedprefilter: the exhaustive Smith-Waterman score filter (M/src/prefiltering/ungappedprefilter.cpp:338-477 with alignmentMode 1:
  * SmithWaterman::ssw_align with Matcher::SCORE_ONLY).  Every query is scored against every target with local Gotoh, gap open 11, gap extend 1,

@@ -39,6 +39,9 @@ uint64_t mk_debug_trace_left_band(const mk_queries *q);
  * profile image, lanes per target for short and for long targets, the target length from which the long shape is used.  The tests place their
  * edge cases with these, so a change of the header moves them */
 void mk_debug_ungapped_constants(int out[6]);
+/* ... and of its kernel for profile queries: lanes per target, diagonals of a band (lanes x diagonals per lane), target positions per image
+ * window, the largest number of targets a lane group takes per band */
+void mk_debug_ungapped_profile_constants(int out[4]);
 /* the same for the gapped prefilter (metaeuk_amd/csrc/mk_gapped.hpp): lanes per target, queries per register, rows per lane of the three tile
  * shapes (a tile is lanes x rows; the last shape walks longer queries in row tiles), blocks of 32 targets per work item */
 void mk_debug_gapped_constants(int out[6]);

@@ -57,6 +57,7 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_default_orf_params", "mk_extract_orfs_ex", "mk_extract_orfs_host", "mk_align_statistics", "mk_align_limit_scan",
            "mk_rescore_diagonal", "mk_rescore_diagonal_host", "mk_alt_alignments", "mk_alt_alignments_host",
            "mk_ungapped_prefilter", "mk_ungapped_prefilter_host", "mk_debug_ungapped_constants",
+           "mk_ungapped_prefilter_profile_host", "mk_debug_ungapped_profile_constants",
            "mk_gapped_prefilter", "mk_gapped_prefilter_host", "mk_debug_gapped_constants"]
 
 
@@ -677,8 +678,14 @@ _UNG_NAMES = ("UNG_DIAGS", "UNG_PACK", "UNG_ROW_TILE", "UNG_GROUP_SHORT", "UNG_G
 _GAP_NAMES = ("GAP_GROUP", "GAP_PACK", "GAP_ROWS_0", "GAP_ROWS_1", "GAP_ROWS_2", "GAP_BLOCKS_PER_WG")
 
 
+# the gapless prefilter's kernel for profile queries: lanes per target, diagonals of a band, target positions per image window, the largest number of
+# targets a lane group takes per band (csrc/mk_ungapped.hpp)
+_UNG_PROF_NAMES = ("UNG_PROF_GROUP", "UNG_PROF_BAND", "UNG_PROF_TILE", "UNG_PROF_MAX_PASSES")
+
+
 def __getattr__(name):
-    for names, fn in ((_UNG_NAMES, "mk_debug_ungapped_constants"), (_GAP_NAMES, "mk_debug_gapped_constants")):
+    for names, fn in ((_UNG_NAMES, "mk_debug_ungapped_constants"), (_GAP_NAMES, "mk_debug_gapped_constants"),
+                      (_UNG_PROF_NAMES, "mk_debug_ungapped_profile_constants")):
         if name in names:
             v = (C.c_int * 6)()
             getattr(lib(), fn)(v)
@@ -702,6 +709,17 @@ def ungapped_prefilter_host(q, t, q_bias8=None, mat=None):
     score = C.c_int()
     _chk(lib().mk_ungapped_prefilter_host(None if m is None else _p(m), _p(q), None if b is None else _p(b), C.c_int(len(q)), _p(tt), C.c_int(len(t)),
                                           C.byref(score)))
+    return int(score.value)
+
+
+def ungapped_prefilter_profile_host(aln32, t):
+    """the score of one (profile, target) pair in the literal byte arithmetic, host code (mk_ungapped_prefilter_profile_host);
+    aln32 = int8 [columns, 32] as Profiles.derived() reports it, t = residue codes"""
+    a = np.ascontiguousarray(aln32, dtype=np.int8).reshape(-1, 32)
+    t = np.ascontiguousarray(t, dtype=np.uint8)
+    tt = t if len(t) else np.zeros(1, dtype=np.uint8)
+    score = C.c_int()
+    _chk(lib().mk_ungapped_prefilter_profile_host(_p(a), C.c_int(len(a)), _p(tt), C.c_int(len(t)), C.byref(score)))
     return int(score.value)
 
 

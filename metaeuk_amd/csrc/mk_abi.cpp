@@ -2226,6 +2226,12 @@ int mk_ungapped_prefilter_host(const int8_t *mat, const uint8_t *q, const int8_t
     return MK_OK;
 }
 
+int mk_ungapped_prefilter_profile_host(const int8_t *aln32, int nCols, const uint8_t *t, int tLen, int *score) {
+    if (!aln32 || !score || nCols <= 0 || tLen < 0 || (!t && tLen > 0)) return fail(MK_ERR_ARG, "mk_ungapped_prefilter_profile_host: null argument, empty profile or negative length");
+    *score = mk::ungapped_profile_pair_host(aln32, nCols, t, tLen);
+    return MK_OK;
+}
+
 // the composition bias this call scores with.  A batch carries the bias of the --comp-bias-corr / --comp-bias-corr-scale it was created with, and
 // every other stage reads that one; a call that brings other values gets its own derivation in scratch memory -- the batch is not touched
 static int ungapped_comp_bias(const mk_queries *q, const mk_params *P, const int8_t **bias8) {
@@ -2280,8 +2286,12 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     int rc = ensure_ready();
     if (rc) return rc;
     if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
-    if (q->isProfile || db->profileSearch || P->profile_search != 0)
-        return fail(MK_ERR_UNSUPPORTED, "ungappedprefilter with profile queries or a profile database is not implemented");
+    // profile queries in the roles of the inverted search (check_roles of mk_search): a profile batch, a database and a call with profile_search = 1
+    const bool profiles = q->isProfile && db->profileSearch && P->profile_search != 0;
+    if (!profiles && (q->isProfile || db->profileSearch || P->profile_search != 0))
+        return fail(MK_ERR_UNSUPPORTED, "ungappedprefilter takes profile queries only as the inverted search does: a profile batch, a target database created with "
+                                        "profile_search = 1 and params->profile_search = 1 (batch: %s, database: %d, params: %d)",
+                    q->isProfile ? "profiles" : "sequences", db->profileSearch ? 1 : 0, P->profile_search);
     if (db->fromIndex)
         return fail(MK_ERR_UNSUPPORTED, "ungappedprefilter against an index DB is not implemented (its sequence lookup is the masked one): pass the sequence DB");
     if ((rc = check_filters(P, false)) != MK_OK) return rc;
@@ -2289,7 +2299,7 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     if (P->min_ungapped_score < 0)
         return fail(MK_ERR_UNSUPPORTED, "--min-ungapped-score %d: a negative threshold keeps pairs of score 0, which the score array does not tell from skipped pairs", P->min_ungapped_score);
     const int8_t *bias8 = nullptr;
-    if ((rc = ungapped_comp_bias(q, P, &bias8)) != MK_OK) return rc;
+    if (!profiles && (rc = ungapped_comp_bias(q, P, &bias8)) != MK_OK) return rc;        // (a profile has no composition bias)
     if ((rc = ungapped_target_orders(db)) != MK_OK) return rc;
     const uint32_t nq = q->n, nt = db->n, maxSeqs = (uint32_t) std::min<int64_t>(P->max_seqs, std::max<uint32_t>(nt, 1));
     q->pfStats = mk::PrefilterStats();
@@ -2314,6 +2324,7 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     const uint32_t nsC = (uint32_t) std::min<uint64_t>(nt, std::max<uint64_t>(1, budget / mk::UNG_PACK));
     uint64_t nqC64 = std::max<uint64_t>(mk::UNG_PACK, budget / nsC / mk::UNG_PACK * mk::UNG_PACK);
     nqC64 = std::min<uint64_t>(nqC64, std::max<uint64_t>(mk::UNG_PACK, ((16ull << 20) / maxSeqs) / mk::UNG_PACK * mk::UNG_PACK));     // (the hit block of a chunk)
+    if (profiles) nqC64 = std::min<uint64_t>(nqC64, 65532);                  // (one profile per grid row)
     const uint32_t nqC = (uint32_t) std::min<uint64_t>(std::min<uint64_t>(nqC64, 65535ull * mk::UNG_PACK), ((uint64_t) nq + mk::UNG_PACK - 1) / mk::UNG_PACK * mk::UNG_PACK);
 
     uint32_t *dQOrder = (uint32_t *) mk::dev_scratch("ungapped_qorder", (size_t) nq * 4);
@@ -2338,13 +2349,14 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     V.cov_thr = P->cov_thr; V.cov_mode = P->cov_mode;
     V.scores = dScores; V.work = dWork;
     V.q0 = V.nq = V.s0 = V.ns = 0;
+    if (profiles) V.p_aln = q->dProfAln.p;
     mk::UngappedSelect S;
     S.key_rank = db->dUngKeyRank.p; S.rank_idx = db->dUngRankIdx.p; S.min_score = P->min_ungapped_score; S.max_seqs = maxSeqs;
     S.cand = dCand; S.cand_cnt = dCnt; S.tmp = dTmp; S.hits = dHits; S.hit_cnt = dHitCnt; S.last = false;
 
     struct FlushTimers { ~FlushTimers() { timed_flush(); } } flushTimers;
     HostTimer ht("host_ungapped_prefilter_total");
-    HIPCHK(mk::launch_ungapped_caps(V, dCaps, g_stream));
+    HIPCHK(profiles ? mk::launch_ungapped_profile_caps(V, dCaps, g_stream) : mk::launch_ungapped_caps(V, dCaps, g_stream));
     std::vector<mk_hit> staged;                      // the chunks' lists in the order of qOrder
     std::vector<uint32_t> cnt(nq, 0);
     // one timer per (query chunk, target chunk); the work counters run over the whole call and are read once, so the LAST timer carries the bytes
@@ -2360,8 +2372,18 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
             if (forceGroup == mk::UNG_GROUP_SHORT) split = V.ns;
             if (forceGroup == mk::UNG_GROUP_LONG) split = 0;
             const int th = lastScoreTimer = timed_begin("ungapped_prefilter", 0, 0);
-            HIPCHK(mk::launch_ungapped_scores(V, 0, split, mk::UNG_GROUP_SHORT, g_stream));
-            HIPCHK(mk::launch_ungapped_scores(V, split, V.ns, mk::UNG_GROUP_LONG, g_stream));
+            if (profiles) {
+                // the targets of at most one window of steps are walked whole inside a band, several per lane group and band -- as many as still leave
+                // the device a few workgroups per compute unit; the longer ones, one per group, window by window
+                const uint32_t whole = (uint32_t) (std::upper_bound(db->ungLens.begin() + s0, db->ungLens.begin() + s0 + V.ns, (uint32_t) mk::UNG_PROF_TILE) - (db->ungLens.begin() + s0));
+                const uint64_t perPass = (uint64_t) (256 / mk::UNG_PROF_GROUP) * 1024;
+                const uint32_t passes = (uint32_t) std::min<uint64_t>(mk::UNG_PROF_MAX_PASSES, std::max<uint64_t>(1, (uint64_t) whole * V.nq / perPass));
+                HIPCHK(mk::launch_ungapped_profile_scores(V, 0, whole, passes, g_stream));
+                HIPCHK(mk::launch_ungapped_profile_scores(V, whole, V.ns, 1, g_stream));
+            } else {
+                HIPCHK(mk::launch_ungapped_scores(V, 0, split, mk::UNG_GROUP_SHORT, g_stream));
+                HIPCHK(mk::launch_ungapped_scores(V, split, V.ns, mk::UNG_GROUP_LONG, g_stream));
+            }
             timed_end(th);
             S.last = s0 + V.ns == nt;
             const int ts = timed_begin("ungapped_select", (double) V.nq * V.ns * 6.0, 0);
@@ -2396,6 +2418,9 @@ int mk_ungapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
 }
 
 // the kernel's work split as the tests read it (metaeuk_amd_debug.h)
+void mk_debug_ungapped_profile_constants(int out[4]) {
+    out[0] = mk::UNG_PROF_GROUP; out[1] = mk::UNG_PROF_BAND; out[2] = mk::UNG_PROF_TILE; out[3] = mk::UNG_PROF_MAX_PASSES;
+}
 void mk_debug_ungapped_constants(int out[6]) {
     out[0] = mk::UNG_DIAGS; out[1] = mk::UNG_PACK; out[2] = mk::UNG_ROW_TILE; out[3] = mk::UNG_GROUP_SHORT; out[4] = mk::UNG_GROUP_LONG; out[5] = mk::UNG_LONG_TARGET;
 }

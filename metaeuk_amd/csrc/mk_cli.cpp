@@ -776,7 +776,9 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     if (profileQueries && isSearch) return die("search with a profile query DB is not a workflow of the reference: use predictexons with a profile target DB, or prefilter / align / swapresults%s");
     if (profileQueries && ungapped) return die("the ungapped alignment stage does not take profile queries (the reference refuses them, Search.cpp:262-266)%s");
     if (profileQueries && altAli > 0) return die("--alt-ali with a profile query database is not implemented%s");
-    if (profileQueries && ungPref) return die("the ungapped prefilter (--prefilter-mode 1) with a profile query database is not implemented%s");
+    // `ungappedprefilter <profileDB> <sequenceDB>` is the exhaustive link of the inverted search (the target side is created with profile_search = 1
+    // below, as P says from here on); the Smith-Waterman filter keeps refusing profiles
+    if (profileQueries && isGappedPref) return die("gappedprefilter with a profile query database is not implemented%s");
     if (profileQueries) { if (int rc = refuseFiltersForProfiles(P)) return rc; P.profile_search = 1; }
     Shard sh;
     if (int rc = shardOf(a, sh, argc, argv)) return rc;

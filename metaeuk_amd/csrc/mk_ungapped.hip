@@ -209,6 +209,138 @@ __global__ __launch_bounds__(256) void ungapped_caps_kernel(UngappedView V, uint
     caps[qi] = (uint8_t) ungapped_cap(ungapped_bias(V.mat_min, biasMin));
 }
 
+// ---- profile queries: the transposed kernel ("Profile queries") ----
+// The long side is the query here (a 300-column profile against a 38-residue fragment), so a lane owns C consecutive diagonals e = i - j and walks the
+// TARGET's positions j: at step j its cells sit on the profile columns e + j .. e + j + 7 of the line of residue t[j].  The profile is the
+// workgroup-uniform side: the image is [residue code][column] int16, so the eight cells of a step are 16 contiguous bytes, and because the window
+// moves by one int16 per step the image is kept twice, the second copy shifted by one column -- an even step reads copy 0, an odd step copy 1, both from
+// a 4-byte-aligned address (two ds_read2_b32), and no cell is shifted in registers.  A lane group of PG lanes covers a band of PG * C diagonals of one
+// target; the PGROUPS groups of a workgroup share the band's image and take `passes` targets each per band, neighbours of the length order, so the image
+// of a band is written once for PGROUPS * passes targets.  The bands of all targets of a workgroup start at diagonal -(longest target - 1): a shorter
+// target only finds pad columns on the diagonals in front of its own first one.  Line 21 is the pad line (a step behind the target's end) and the
+// columns outside [0, Lp) hold -32768 on every line: the clamped add clears the state there.  Targets longer than PTILE steps are walked window by
+// window (the states stay in registers, the window is written again per band and tile) with one target per group.
+constexpr int PG = UNG_PROF_GROUP, PGROUPS = 256 / PG, PBAND = UNG_PROF_BAND, PTILE = UNG_PROF_TILE, PCOLS = PBAND + PTILE;
+constexpr int PLINES = 22, PPAD_LINE = 21, PLINE_BYTES = PCOLS * 2, PCOPY_DW = PLINES * PCOLS / 2, PCOPY_BYTES = PCOPY_DW * 4;
+static_assert(PG == 16, "a lane group is one DPP row");
+static_assert(PTILE % C == 0 && PBAND % C == 0 && 2 * PCOPY_BYTES <= 65536, "whole step blocks; two copies of the window within LDS");
+
+__device__ __forceinline__ void workgroup_sync_lds() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+// what the image holds for (line, column) of the profile at `aln`
+__device__ __forceinline__ uint32_t profile_cell(const int8_t *aln, int lp, int line, int col) {
+    if (line == PPAD_LINE || col < 0 || col >= lp) return 0x8000u;
+    return (uint32_t) ungapped_profile_score(aln + (size_t) col * 32, line) & 0xFFFFu;
+}
+
+__global__ __launch_bounds__(256) void ungapped_profile_scores_kernel(UngappedView V, uint32_t a, uint32_t b, uint32_t passes) {
+    __shared__ uint32_t sImg[2 * PCOPY_DW];
+    __shared__ uint16_t sBest[UNG_PROF_MAX_PASSES * PGROUPS];
+    __shared__ unsigned long long sWork[2];
+    const uint32_t tid = threadIdx.x, sub = tid % PG, grp = tid / PG;
+    const uint32_t row = blockIdx.y, pi = V.q_order[V.q0 + row];
+    const uint64_t pOff = V.q_off[pi];
+    const int lp = (int) (V.q_off[pi + 1] - pOff);
+    const int8_t *aln = V.p_aln + pOff * 32;
+    // this workgroup's targets: `passes` per lane group, neighbours of the length order; the longest is the last
+    const uint32_t run0 = a + blockIdx.x * PGROUPS * passes, runEnd = min(b, run0 + PGROUPS * passes);
+    int maxLt = 0;
+    { const uint32_t tl = V.t_order[V.s0 + runEnd - 1]; maxLt = (int) (V.t_off[tl + 1] - V.t_off[tl]); }
+    for (uint32_t k = tid; k < passes * PGROUPS; k += 256) sBest[k] = 0;
+    if (tid < 2) sWork[tid] = 0;
+    workgroup_sync_lds();
+    const int nBands = (lp > 0 && maxLt > 0) ? (lp + maxLt - 1 + PBAND - 1) / PBAND : 0, nTiles = (maxLt + PTILE - 1) / PTILE;
+
+    for (int band = 0; band < nBands; band++) {
+        const int e0 = -(maxLt - 1) + band * PBAND;               // the band's first diagonal; this lane's: e0 + sub * C
+        for (uint32_t pass = 0; pass < passes; pass++) {
+            const uint32_t pos = run0 + pass * PGROUPS + grp;
+            uint32_t tLen = 0; uint64_t tOff = 0;
+            if (pos < runEnd) { const uint32_t ti = V.t_order[V.s0 + pos]; tOff = V.t_off[ti]; tLen = (uint32_t) (V.t_off[ti + 1] - tOff); }
+            TargetWin T;
+            T.words = (const uint32_t *) (V.t_res + (tOff & ~(uint64_t) 3)); T.r0 = (int) (tOff & 3); T.len = tLen;
+            v2s st[C / 2], m0 = (v2s) (short) 0, m1 = (v2s) (short) 0;
+#pragma unroll
+            for (int k = 0; k < C / 2; k++) st[k] = (v2s) (short) 0;
+            uint32_t lo = 0, hi = 0;
+            fetch8(T, 0, lo, hi);
+            for (int tile = 0; tile < nTiles; tile++) {
+                const int j0 = tile * PTILE, nBlocks = (min(PTILE, maxLt - j0) + C - 1) / C;
+                if (pass == 0 || nTiles > 1) {
+                    // the window of (band, tile): slot s of copy 0 is column e0 + j0 + s, of copy 1 column e0 + j0 + s + 1
+                    for (uint32_t e = tid; e < (uint32_t) PCOPY_DW; e += 256) {
+                        const int line = (int) (e / (PCOLS / 2)), col = e0 + j0 + 2 * (int) (e % (PCOLS / 2));
+                        const uint32_t v0 = profile_cell(aln, lp, line, col), v1 = profile_cell(aln, lp, line, col + 1), v2 = profile_cell(aln, lp, line, col + 2);
+                        sImg[e] = v0 | (v1 << 16);
+                        sImg[PCOPY_DW + e] = v1 | (v2 << 16);
+                    }
+                    workgroup_sync_lds();
+                }
+                for (int blk = 0; blk < nBlocks; blk++) {
+                    const uint32_t cl = lo, ch = hi, j = (uint32_t) (j0 + blk * C);
+                    fetch8(T, (int) j + C, lo, hi);                    // the residues of the next block, a block ahead of their use
+                    const uint32_t base = (sub + (uint32_t) blk) * (C * 2);
+#pragma unroll
+                    for (int r = 0; r < C; r++) {
+                        const uint32_t code = ((r < 4 ? cl : ch) >> (8 * (r & 3))) & 0xFFu;
+                        const uint32_t line = j + r < tLen ? min(code, 20u) : (uint32_t) PPAD_LINE;
+                        const uint32_t *p = (const uint32_t *) ((const char *) sImg + line * PLINE_BYTES + base + (r & 1) * PCOPY_BYTES + (r & ~1) * 2);
+#pragma unroll
+                        for (int k = 0; k < C / 2; k++) st[k] = cell2(st[k], p[k]);
+                        m0 = vmax(m0, vmax(st[0], st[1])); m1 = vmax(m1, vmax(st[2], st[3]));
+                    }
+                }
+                if (nTiles > 1) workgroup_sync_lds();                  // the window is read out before the next one overwrites it
+            }
+            // the maximum of this (band, target) over the group's lanes; its first lane keeps the target's maximum over the bands
+            uint32_t g = as_u32(vmax(m0, m1));
+            g = as_u32(vmax(as_v2s(g), as_v2s(dpp<0xB1>(g))));         // quad_perm [1, 0, 3, 2]
+            g = as_u32(vmax(as_v2s(g), as_v2s(dpp<0x4E>(g))));         // quad_perm [2, 3, 0, 1]
+            g = as_u32(vmax(as_v2s(g), as_v2s(dpp<0x141>(g))));        // row_half_mirror
+            g = as_u32(vmax(as_v2s(g), as_v2s(dpp<0x140>(g))));        // row_mirror
+            if (sub == 0) {
+                const uint32_t best = max(g & 0xFFFFu, g >> 16);       // (the halves are not negative)
+                sBest[pass * PGROUPS + grp] = (uint16_t) max(best, (uint32_t) sBest[pass * PGROUPS + grp]);
+            }
+        }
+        if (nTiles == 1) workgroup_sync_lds();                         // every pass has read the band's window
+    }
+
+    if (sub == 0) {
+        unsigned long long cells = 0, bytes = 0;
+        const int cap = (int) V.q_cap[pi];
+        for (uint32_t pass = 0; pass < passes; pass++) {
+            const uint32_t pos = run0 + pass * PGROUPS + grp;
+            if (pos >= runEnd) continue;
+            const uint32_t ti = V.t_order[V.s0 + pos], tLen = (uint32_t) (V.t_off[ti + 1] - V.t_off[ti]);
+            int score = 0;
+            if (ungapped_pair_scored(V.cov_thr, V.cov_mode, (uint32_t) lp, tLen)) {
+                score = min(cap, (int) sBest[pass * PGROUPS + grp]);
+                cells += (unsigned long long) lp * tLen;
+            }
+            V.scores[(size_t) row * V.ns + pos] = (uint8_t) score;
+            bytes += (unsigned long long) tLen + 1;
+        }
+        atomicAdd(&sWork[0], bytes);
+        atomicAdd(&sWork[1], cells);
+    }
+    __syncthreads();
+    if (tid < 2 && sWork[tid]) atomicAdd(&V.work[tid], sWork[tid]);
+}
+
+// one wave per profile: the smallest amino-acid score of its columns
+__global__ __launch_bounds__(256) void ungapped_profile_caps_kernel(UngappedView V, uint8_t *caps) {
+    const uint32_t qi = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
+    if (qi >= V.n_queries) return;
+    int m = 0;
+    for (uint64_t c = V.q_off[qi] + lane; c < V.q_off[qi + 1]; c += 64) m = min(m, ungapped_profile_col_min(V.p_aln + c * 32));
+    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+    if (lane == 0) caps[qi] = (uint8_t) ungapped_cap(ungapped_bias(m, 0));
+}
+
 constexpr uint32_t SORT_TILE = 2048;
 __global__ __launch_bounds__(256) void ungapped_select_kernel(UngappedView V, UngappedSelect S) {
     __shared__ uint32_t sHist[256];
@@ -303,6 +435,20 @@ hipError_t launch_ungapped_scores(const UngappedView &V, uint32_t a, uint32_t b,
     const dim3 grid((b - a + perBlock - 1) / perBlock, qGroups);
     if (group == UNG_GROUP_SHORT) hipLaunchKernelGGL(ungapped_scores_kernel<UNG_GROUP_SHORT>, grid, dim3(256), 0, stream, V, a, b);
     else hipLaunchKernelGGL(ungapped_scores_kernel<UNG_GROUP_LONG>, grid, dim3(256), 0, stream, V, a, b);
+    return hipGetLastError();
+}
+
+hipError_t launch_ungapped_profile_caps(const UngappedView &V, uint8_t *caps, hipStream_t stream) {
+    if (V.n_queries == 0) return hipSuccess;
+    hipLaunchKernelGGL(ungapped_profile_caps_kernel, dim3((V.n_queries + 3) / 4), dim3(256), 0, stream, V, caps);
+    return hipGetLastError();
+}
+
+hipError_t launch_ungapped_profile_scores(const UngappedView &V, uint32_t a, uint32_t b, uint32_t passes, hipStream_t stream) {
+    if (b <= a || V.nq == 0) return hipSuccess;
+    if (b > V.ns || passes < 1 || passes > (uint32_t) UNG_PROF_MAX_PASSES || V.nq > 65535u || !V.p_aln) return hipErrorInvalidValue;
+    const uint32_t perBlock = PGROUPS * passes;
+    hipLaunchKernelGGL(ungapped_profile_scores_kernel, dim3((b - a + perBlock - 1) / perBlock, V.nq), dim3(256), 0, stream, V, a, b, passes);
     return hipGetLastError();
 }
 

@@ -13,6 +13,11 @@
 // = max(0, min(S + (b - bias), 255 - bias)).  A capped and an uncapped run agree until the first cell that reaches 255 - bias; from there the capped
 // maximum is 255 - bias and the uncapped one at least that.  So score = min(255 - bias, max over cells of U), U(i, j) = max(0, U(i-1, j-1) + (b - bias))
 // in anything wide enough (saturating int16 here: a U that sticks at 32767 has long passed the cap).
+// Profile queries (the inverted search of a profile target database: ungappedprefilter.cpp:373-374 hands qSeq.getAlignmentProfile() to ssw_init).
+// The byte of column i and residue a is P[i][a] + bias with P the int8 alignment profile (the 20 amino-acid entries of the [column][32] array of
+// mk_profile.hpp), X (code 20, and any code above it) scores 0 in every column (ssw_init clears that row, StripedSmithWaterman.cpp:1243-1244),
+// bias = |min(0, the 20 amino-acid scores of all columns)| (:1276-1287 with matSize = L * PROFILE_AA_SIZE), and a profile has no composition bias.
+// The recurrence, the commuted form, the verdicts, the order and the cut are the ones above: ungapped_profile_* below and the same helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -74,6 +79,34 @@ inline int ungapped_pair_host(const int8_t *mat, const uint8_t *q, const int8_t 
     return best;
 }
 
+// ---- profile queries ----
+// the work split of ungapped_profile_scores_kernel: lanes per target (a band is UNG_PROF_GROUP * UNG_DIAGS diagonals), target positions per
+// image window, the largest number of targets a lane group takes per band
+constexpr int UNG_PROF_GROUP = 16, UNG_PROF_BAND = UNG_PROF_GROUP * UNG_DIAGS, UNG_PROF_TILE = 128, UNG_PROF_MAX_PASSES = 16;
+// what column `col` ([32] int8, mk_profile.hpp) scores for residue code `code`
+__host__ __device__ inline int ungapped_profile_score(const int8_t *col, int code) { return code < 20 ? (int) col[code] : 0; }
+// the smallest amino-acid score of a column and 0
+__host__ __device__ inline int ungapped_profile_col_min(const int8_t *col) {
+    int m = 0;
+    for (int a = 0; a < 20; a++) m = col[a] < m ? col[a] : m;
+    return m;
+}
+// one pair, cell by cell, in the literal byte arithmetic (the twin).  aln32 = [nCols][32] int8
+inline int ungapped_profile_pair_host(const int8_t *aln32, int nCols, const uint8_t *t, int tLen) {
+    int pMin = 0;
+    for (int i = 0; i < nCols; i++) { const int m = ungapped_profile_col_min(aln32 + (size_t) i * 32); pMin = m < pMin ? m : pMin; }
+    const int bias = ungapped_bias(pMin, 0);
+    uint8_t best = 0;
+    for (int e = -(tLen - 1); e < nCols; e++) {         // diagonal e: target position j meets column e + j
+        uint8_t s = 0;
+        for (int j = e < 0 ? -e : 0; j < tLen && e + j < nCols; j++) {
+            s = ungapped_step(s, ungapped_profile_byte(ungapped_profile_score(aln32 + (size_t) (e + j) * 32, t[j]), 0, bias), (uint8_t) bias);
+            best = s > best ? s : best;
+        }
+    }
+    return best;
+}
+
 // ---- the kernel side (mk_ungapped.hip) ----
 struct UngappedView {
     const uint8_t *q_res; const uint64_t *q_off; const int8_t *q_bias8; uint32_t n_queries;
@@ -88,9 +121,15 @@ struct UngappedView {
     uint32_t s0, ns;                           // the chunk's targets: positions [s0, s0 + ns) of t_order
     uint8_t *scores;                           // [nq][ns] one byte per pair, 0 for a skipped pair
     unsigned long long *work;                  // [0] algorithmic bytes, [1] cells
+    const int8_t *p_aln = nullptr;             // profile queries: [column][32] alignment profile, q_off the column offsets (q_res, q_bias8, mat unused)
 };
 // 255 - bias of every query
 hipError_t launch_ungapped_caps(const UngappedView &V, uint8_t *caps, hipStream_t stream);
+// the same for every profile of a profile batch (V.p_aln)
+hipError_t launch_ungapped_profile_caps(const UngappedView &V, uint8_t *caps, hipStream_t stream);
+// profile queries: the scores of positions [a, b) of the chunk's targets, every lane group taking `passes` targets per band of diagonals
+// (1 .. UNG_PROF_MAX_PASSES; 1 when a target of the range is longer than UNG_PROF_TILE)
+hipError_t launch_ungapped_profile_scores(const UngappedView &V, uint32_t a, uint32_t b, uint32_t passes, hipStream_t stream);
 // the scores of positions [a, b) of the chunk's targets with `group` lanes per target (UNG_GROUP_SHORT or UNG_GROUP_LONG)
 hipError_t launch_ungapped_scores(const UngappedView &V, uint32_t a, uint32_t b, int group, hipStream_t stream);
 // the best max_seqs hits of every query of the chunk over the chunk's targets and the candidates kept from earlier target chunks (cand / cand_cnt, in
