@@ -332,12 +332,22 @@ int mk_ungapped_prefilter_profile_host(const int8_t *aln32, int n_cols, const ui
  * index, pref_score = score, diagonal 0): mk_prefilter_result, mk_align, mk_rescore_diagonal and the formatters read it unchanged.  Works on
  * mk_targetdb_create_sequences and mk_targetdb_create databases.  Honoured of params: max_seqs, min_ungapped_score, evalue_thr, comp_bias_corr,
  * comp_bias_scale (the rule of mk_ungapped_prefilter: other values than the batch's are derived into scratch memory), cov_thr, cov_mode.
- * Residue codes above 20 are read as X.  MK_ERR_UNSUPPORTED: profile queries or a profile database, a database opened from an index DB, a
- * negative min_ungapped_score, gap costs other than 11 / 1. */
+ * Residue codes above 20 are read as X.  MK_ERR_UNSUPPORTED: profile queries or a profile database (they go through
+ * mk_gapped_prefilter_profile), a database opened from an index DB, a negative min_ungapped_score, gap costs other than 11 / 1. */
 int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *params);
+/* the same filter for profile queries (`gappedprefilter <profileDB> <sequenceDB>`, the exhaustive gapped link of the inverted search of a profile
+ * target database), in the roles mk_ungapped_prefilter takes them: a batch of mk_profiles_create, a database created with
+ * params->profile_search = 1 and a call with params->profile_search = 1.  Column i and residue a score P[i][a], the batch's int8 alignment profile
+ * (aln32 of mk_profiles_derived, entries 0 .. 19); X, and every target code above 20, scores 0 in every column; there is no composition bias; the
+ * gap costs are the uniform 11 / 1 (ssw_init on a profile, StripedSmithWaterman.cpp:1228-1247).  Cell arithmetic, cap, verdicts, order, cut and
+ * result are those of mk_gapped_prefilter with the profile's column count as the query length.  MK_ERR_UNSUPPORTED: any other combination of
+ * batch, database and params->profile_search, a database opened from an index DB, a negative min_ungapped_score, gap costs other than 11 / 1. */
+int mk_gapped_prefilter_profile(mk_targetdb *db, mk_queries *q, const mk_params *params);
 /* the score of ONE pair, host code without a GPU and without mk_init (the twin the kernel is checked against): the plain row loop in 32-bit
  * integers.  Arguments as for mk_ungapped_prefilter_host. */
 int mk_gapped_prefilter_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int q_len, const uint8_t *t, int t_len, int *score);
+/* the same for ONE (profile, target) pair.  Arguments as for mk_ungapped_prefilter_profile_host. */
+int mk_gapped_prefilter_profile_host(const int8_t *aln32, int n_cols, const uint8_t *t, int t_len, int *score);
 
 /* ---- --alt-ali N: alternative alignments (Alignment::computeAlternativeAlignment, M/src/alignment/Alignment.cpp:399-401, 569-601).  Runs after
  * mk_align / mk_search on the batch's alignment result and replaces it with the merged lists; mk_align_result and mk_format_alignment read it

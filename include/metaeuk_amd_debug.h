@@ -45,6 +45,10 @@ void mk_debug_ungapped_profile_constants(int out[4]);
 /* the same for the gapped prefilter (metaeuk_amd/csrc/mk_gapped.hpp): lanes per target, queries per register, rows per lane of the three tile
  * shapes (a tile is lanes x rows; the last shape walks longer queries in row tiles), blocks of 32 targets per work item */
 void mk_debug_gapped_constants(int out[6]);
+/* ... and of its kernel for profile queries, which puts the target into the rows of those shapes: the profile's columns per block, the columns the
+ * last lane of a target lags behind the first, the columns of steps one image window holds (a profile of more than window - lag columns takes
+ * several), the longest target it takes (longer ones go through the row-tiled kernel) */
+void mk_debug_gapped_profile_constants(int out[4]);
 
 /* ---- experiment hook (tools/micro/mk_experiments.hip is its only user): the device view of a (database, batch) pair -- a
  * mk::PrefilterDeviceView (metaeuk_amd/csrc/mk_prefilter.hpp: pointers into HBM, valid while both handles live) copied into view_out, whose

@@ -58,7 +58,8 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_rescore_diagonal", "mk_rescore_diagonal_host", "mk_alt_alignments", "mk_alt_alignments_host",
            "mk_ungapped_prefilter", "mk_ungapped_prefilter_host", "mk_debug_ungapped_constants",
            "mk_ungapped_prefilter_profile_host", "mk_debug_ungapped_profile_constants",
-           "mk_gapped_prefilter", "mk_gapped_prefilter_host", "mk_debug_gapped_constants"]
+           "mk_gapped_prefilter", "mk_gapped_prefilter_host", "mk_debug_gapped_constants",
+           "mk_gapped_prefilter_profile", "mk_gapped_prefilter_profile_host", "mk_debug_gapped_profile_constants"]
 
 
 def lib():
@@ -683,9 +684,14 @@ _GAP_NAMES = ("GAP_GROUP", "GAP_PACK", "GAP_ROWS_0", "GAP_ROWS_1", "GAP_ROWS_2",
 _UNG_PROF_NAMES = ("UNG_PROF_GROUP", "UNG_PROF_BAND", "UNG_PROF_TILE", "UNG_PROF_MAX_PASSES")
 
 
+# the gapped prefilter's kernel for profile queries (the target in the rows of the GAP_ROWS shapes): the profile's columns per block, the columns the
+# last lane of a target lags behind the first, the columns of steps per image window, the longest target it takes (csrc/mk_gapped.hpp)
+_GAP_PROF_NAMES = ("GAPP_BLOCK", "GAPP_LAG", "GAPP_WINDOW", "GAPP_MAX_TARGET")
+
+
 def __getattr__(name):
     for names, fn in ((_UNG_NAMES, "mk_debug_ungapped_constants"), (_GAP_NAMES, "mk_debug_gapped_constants"),
-                      (_UNG_PROF_NAMES, "mk_debug_ungapped_profile_constants")):
+                      (_UNG_PROF_NAMES, "mk_debug_ungapped_profile_constants"), (_GAP_PROF_NAMES, "mk_debug_gapped_profile_constants")):
         if name in names:
             v = (C.c_int * 6)()
             getattr(lib(), fn)(v)
@@ -739,6 +745,25 @@ def gapped_prefilter_host(q, t, q_bias8=None, mat=None):
     score = C.c_int()
     _chk(lib().mk_gapped_prefilter_host(None if m is None else _p(m), _p(q), None if b is None else _p(b), C.c_int(len(q)), _p(tt), C.c_int(len(t)),
                                         C.byref(score)))
+    return int(score.value)
+
+
+def gapped_prefilter_profile(db, q, params=None):
+    """gappedprefilter with profile queries in the roles of the inverted search (mk_gapped_prefilter_profile) -> (hits structured array [total],
+    offsets uint64[n+1])"""
+    p = params or db.params
+    _chk(lib().mk_gapped_prefilter_profile(db.h, q.h, C.byref(p)))
+    return prefilter_result(q)
+
+
+def gapped_prefilter_profile_host(aln32, t):
+    """the Smith-Waterman score of one (profile, target) pair by the plain row loop, host code (mk_gapped_prefilter_profile_host);
+    aln32 = int8 [columns, 32] as Profiles.derived() reports it, t = residue codes"""
+    a = np.ascontiguousarray(aln32, dtype=np.int8).reshape(-1, 32)
+    t = np.ascontiguousarray(t, dtype=np.uint8)
+    tt = t if len(t) else np.zeros(1, dtype=np.uint8)
+    score = C.c_int()
+    _chk(lib().mk_gapped_prefilter_profile_host(_p(a), C.c_int(len(a)), _p(tt), C.c_int(len(t)), C.byref(score)))
     return int(score.value)
 
 

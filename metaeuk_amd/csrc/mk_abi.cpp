@@ -2442,9 +2442,9 @@ int mk_gapped_prefilter_host(const int8_t *mat, const uint8_t *q, const int8_t *
 // the launches of one (query chunk, target chunk): the chunk's query pairs by tile shape (the queries are sorted by length, so a shape is a range
 // of pairs), and for the pairs beyond the largest tile the target ranges by length class, each with as many workgroups as its parked rows leave room for
 struct GappedParkLaunch { uint32_t a, b, stride, blocks; };
-static void gapped_park_plan(const std::vector<uint32_t> &lens, uint32_t s0, uint32_t ns, uint32_t pairs, std::vector<GappedParkLaunch> &out) {
+static void gapped_park_plan(const std::vector<uint32_t> &lens, uint32_t s0, uint32_t a0, uint32_t ns, uint32_t pairs, std::vector<GappedParkLaunch> &out) {
     out.clear();
-    uint32_t a = 0;
+    uint32_t a = a0;                                              // (profile queries: the chunk's targets in front of a0 take the transposed kernel)
     for (uint64_t limit = 512; a < ns; limit *= 4) {              // length classes 1 .. 512, .. 2048, .. 8192, ...: a strip is as long as its class's longest target
         const uint32_t b = (uint32_t) (std::upper_bound(lens.begin() + s0 + a, lens.begin() + s0 + ns, (uint32_t) std::min<uint64_t>(limit, UINT32_MAX)) - (lens.begin() + s0));
         if (b == a) continue;
@@ -2458,12 +2458,10 @@ static void gapped_park_plan(const std::vector<uint32_t> &lens, uint32_t s0, uin
     }
 }
 
-int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
-    int rc = ensure_ready();
-    if (rc) return rc;
-    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
-    if (q->isProfile || db->profileSearch || P->profile_search != 0)
-        return fail(MK_ERR_UNSUPPORTED, "gappedprefilter with profile queries or a profile database is not implemented");
+// what mk_gapped_prefilter and mk_gapped_prefilter_profile share: everything behind the check of the roles.  profiles: the batch is a profile batch,
+// a query's length is its column count, and the score kernels read the alignment profile instead of residues, composition bias and matrix
+static int gapped_prefilter_run(mk_targetdb *db, mk_queries *q, const mk_params *P, bool profiles) {
+    int rc;
     if (db->fromIndex)
         return fail(MK_ERR_UNSUPPORTED, "gappedprefilter against an index DB is not implemented (its sequence lookup is the masked one): pass the sequence DB");
     if ((rc = check_filters(P, false)) != MK_OK) return rc;
@@ -2472,9 +2470,20 @@ int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
         return fail(MK_ERR_UNSUPPORTED, "--min-ungapped-score %d: a negative threshold keeps pairs of score 0, which the score array does not tell from skipped pairs", P->min_ungapped_score);
     if (P->gap_open != mk::GAP_OPEN || P->gap_extend != mk::GAP_EXTEND)
         return fail(MK_ERR_UNSUPPORTED, "gappedprefilter with gap costs %d / %d: only %d / %d have a Gumbel parameter set in the reference", P->gap_open, P->gap_extend, mk::GAP_OPEN, mk::GAP_EXTEND);
+    // MK_GAPPED_PROFILE_ROUTE=rows (a debug switch): every target of a profile call takes the row-tiled kernel, the A/B of the transposed one
+    bool rowsOnly = false;
+    if (const char *k = profiles ? mk::knob("MK_GAPPED_PROFILE_ROUTE") : nullptr) {
+        if (strcmp(k, "rows") != 0) return fail(MK_ERR_ARG, "MK_GAPPED_PROFILE_ROUTE=%s: the only route to force is `rows`", k);
+        rowsOnly = true;
+    }
     const int8_t *bias8 = nullptr;
-    if ((rc = ungapped_comp_bias(q, P, &bias8)) != MK_OK) return rc;
+    if (!profiles && (rc = ungapped_comp_bias(q, P, &bias8)) != MK_OK) return rc;        // (a profile has no composition bias)
     if ((rc = ungapped_target_orders(db)) != MK_OK) return rc;                  // the orders of the target side are the gapless stage's
+    // profile queries: the first position of a target chunk that takes the row-tiled kernel (the targets are ordered by length)
+    const auto firstRowTiled = [&](uint32_t s0, uint32_t ns) {
+        if (!profiles || rowsOnly) return 0u;
+        return (uint32_t) (std::upper_bound(db->ungLens.begin() + s0, db->ungLens.begin() + s0 + ns, (uint32_t) mk::GAPP_MAX_TARGET) - (db->ungLens.begin() + s0));
+    };
     const uint32_t nq = q->n, nt = db->n, maxSeqs = (uint32_t) std::min<int64_t>(P->max_seqs, std::max<uint32_t>(nt, 1));
     q->pfStats = mk::PrefilterStats();
     q->hitOff.assign((size_t) nq + 1, 0);
@@ -2515,7 +2524,7 @@ int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
         for (uint32_t p = 0; p < pairs; p++) longPairs += qLenAt(q0 + std::min(2 * p + 1, n - 1)) > (uint32_t) mk::GAP_MAX_TILE;
         if (!longPairs) continue;
         for (uint32_t s0 = 0; s0 < nt; s0 += nsC) {
-            gapped_park_plan(db->ungLens, s0, std::min(nsC, nt - s0), longPairs, parkPlan);
+            gapped_park_plan(db->ungLens, s0, firstRowTiled(s0, std::min(nsC, nt - s0)), std::min(nsC, nt - s0), longPairs, parkPlan);
             for (const GappedParkLaunch &L : parkPlan) parkBytes = std::max<uint64_t>(parkBytes, (uint64_t) L.blocks * mk::gapped_park_strips() * L.stride * sizeof(uint2));
         }
     }
@@ -2540,6 +2549,7 @@ int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     V.cov_thr = P->cov_thr; V.cov_mode = P->cov_mode;
     V.scores = dScores; V.work = dWork; V.gate = dGate;
     V.q0 = V.nq = V.s0 = V.ns = 0;
+    if (profiles) V.p_aln = q->dProfAln.p;
     mk::GappedSelect S;
     S.key_rank = db->dUngKeyRank.p; S.rank_idx = db->dUngRankIdx.p; S.min_score = P->min_ungapped_score; S.max_seqs = maxSeqs;
     S.cand = dCand; S.cand_cnt = dCnt; S.tmp = dTmp; S.hits = dHits; S.hit_cnt = dHitCnt; S.last = false;
@@ -2564,9 +2574,18 @@ int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
         for (uint32_t s0 = 0; s0 < nt; s0 += nsC) {
             V.s0 = s0; V.ns = std::min(nsC, nt - s0);
             const int th = lastScoreTimer = timed_begin("gapped_prefilter", 0, 0);
-            for (int k = 0; k < mk::GAP_SHAPES; k++) HIPCHK(mk::launch_gapped_scores(V, k, edge[k], edge[k + 1], 0, V.ns, nullptr, 0, 0, g_stream));
-            if (edge[mk::GAP_SHAPES] < pairs) {
-                gapped_park_plan(db->ungLens, s0, V.ns, pairs - edge[mk::GAP_SHAPES], parkPlan);
+            // profile queries: the targets of at most GAPP_MAX_TARGET residues go into the rows of the transposed kernel, by shape; the longer ones
+            // (a0 and beyond) take the row-tiled kernel below, as every target of a sequence call does
+            const uint32_t a0 = firstRowTiled(s0, V.ns);
+            for (uint32_t k = 0, from = 0; k < (uint32_t) mk::GAP_SHAPES && from < a0; k++) {
+                const uint32_t rows = (uint32_t) (mk::GAP_GROUP * mk::gapped_shape_rows((int) k));
+                const uint32_t to = (uint32_t) (std::upper_bound(db->ungLens.begin() + s0 + from, db->ungLens.begin() + s0 + a0, rows) - (db->ungLens.begin() + s0));
+                HIPCHK(mk::launch_gapped_profile_scores(V, (int) k, from, to, g_stream));
+                from = to;
+            }
+            for (int k = 0; k < mk::GAP_SHAPES; k++) HIPCHK(mk::launch_gapped_scores(V, k, edge[k], edge[k + 1], a0, V.ns, nullptr, 0, 0, g_stream));
+            if (edge[mk::GAP_SHAPES] < pairs && a0 < V.ns) {
+                gapped_park_plan(db->ungLens, s0, a0, V.ns, pairs - edge[mk::GAP_SHAPES], parkPlan);
                 for (const GappedParkLaunch &L : parkPlan)
                     HIPCHK(mk::launch_gapped_scores(V, mk::GAP_SHAPES - 1, edge[mk::GAP_SHAPES], pairs, L.a, L.b, dPark, L.stride, L.blocks, g_stream));
             }
@@ -2603,7 +2622,37 @@ int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
     return MK_OK;
 }
 
-// the kernel's work split as the tests read it (metaeuk_amd_debug.h)
+int mk_gapped_prefilter(mk_targetdb *db, mk_queries *q, const mk_params *P) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
+    if (q->isProfile || db->profileSearch || P->profile_search != 0)
+        return fail(MK_ERR_UNSUPPORTED, "mk_gapped_prefilter takes sequence queries: profile queries in the roles of the inverted search go through mk_gapped_prefilter_profile");
+    return gapped_prefilter_run(db, q, P, false);
+}
+
+int mk_gapped_prefilter_profile(mk_targetdb *db, mk_queries *q, const mk_params *P) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
+    // the roles of the inverted search, as mk_ungapped_prefilter takes them
+    if (!q->isProfile || !db->profileSearch || P->profile_search == 0)
+        return fail(MK_ERR_UNSUPPORTED, "mk_gapped_prefilter_profile takes profile queries as the inverted search does: a profile batch, a target database created with "
+                                        "profile_search = 1 and params->profile_search = 1 (batch: %s, database: %d, params: %d)",
+                    q->isProfile ? "profiles" : "sequences", db->profileSearch ? 1 : 0, P->profile_search);
+    return gapped_prefilter_run(db, q, P, true);
+}
+
+int mk_gapped_prefilter_profile_host(const int8_t *aln32, int nCols, const uint8_t *t, int tLen, int *score) {
+    if (!aln32 || !score || nCols <= 0 || tLen < 0 || (!t && tLen > 0)) return fail(MK_ERR_ARG, "mk_gapped_prefilter_profile_host: null argument, empty profile or negative length");
+    *score = mk::gapped_profile_pair_host(aln32, nCols, t, tLen);
+    return MK_OK;
+}
+
+// the kernels' work split as the tests read it (metaeuk_amd_debug.h)
+void mk_debug_gapped_profile_constants(int out[4]) {
+    out[0] = mk::GAPP_BLOCK; out[1] = mk::GAPP_LAG; out[2] = mk::GAPP_WINDOW; out[3] = mk::GAPP_MAX_TARGET;
+}
 void mk_debug_gapped_constants(int out[6]) {
     out[0] = mk::GAP_GROUP; out[1] = mk::GAP_PACK;
     for (int k = 0; k < mk::GAP_SHAPES; k++) out[2 + k] = mk::gapped_shape_rows(k);

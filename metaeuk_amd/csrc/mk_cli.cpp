@@ -671,7 +671,8 @@ int openTargetSequences(const mk::Database &tdb, const mk_params &P, TargetSide 
 // (ungappedprefilter.cpp:393-397); the alignment stage behind it reads the letters as always.  A database with such letters is therefore
 // given to the stage as a second, residues-only database with the same target order.
 int ungappedStage(const mk::Database &tdb, mk_targetdb *T, const std::vector<uint32_t> &keys, mk_queries *Q, const mk_params &P, bool gapped = false) {
-    const auto stage = gapped ? mk_gapped_prefilter : mk_ungapped_prefilter;
+    // (profile queries, P.profile_search = 1: the gapless call takes both kinds of batch, the Smith-Waterman filter has a call for each)
+    const auto stage = gapped ? (P.profile_search ? mk_gapped_prefilter_profile : mk_gapped_prefilter) : mk_ungapped_prefilter;
     bool masked = false;
     for (size_t i = 0; i < tdb.entries.size() && !masked; i++) {
         const char *s = tdb.entry(i);
@@ -776,9 +777,8 @@ int cmdPrefilterOrAlign(int mode, int argc, char **argv) {
     if (profileQueries && isSearch) return die("search with a profile query DB is not a workflow of the reference: use predictexons with a profile target DB, or prefilter / align / swapresults%s");
     if (profileQueries && ungapped) return die("the ungapped alignment stage does not take profile queries (the reference refuses them, Search.cpp:262-266)%s");
     if (profileQueries && altAli > 0) return die("--alt-ali with a profile query database is not implemented%s");
-    // `ungappedprefilter <profileDB> <sequenceDB>` is the exhaustive link of the inverted search (the target side is created with profile_search = 1
-    // below, as P says from here on); the Smith-Waterman filter keeps refusing profiles
-    if (profileQueries && isGappedPref) return die("gappedprefilter with a profile query database is not implemented%s");
+    // `ungappedprefilter <profileDB> <sequenceDB>` and `gappedprefilter <profileDB> <sequenceDB>` are the exhaustive links of the inverted search (the
+    // target side is created with profile_search = 1 below, as P says from here on)
     if (profileQueries) { if (int rc = refuseFiltersForProfiles(P)) return rc; P.profile_search = 1; }
     Shard sh;
     if (int rc = shardOf(a, sh, argc, argv)) return rc;

@@ -15,6 +15,9 @@
 // a wave finish together; a workgroup takes the items blockIdx.x, blockIdx.x + gridDim.x, ...  Queries beyond the largest tile run in row tiles with
 // the last shape: the bottom row (H and F of both queries, 8 B per column) is parked in device memory, one strip per target in flight, written
 // by the group's last lane and read by its first lane of the next tile seven steps ahead of the write to the same column.
+// Profile queries (mk_gapped_prefilter_profile): targets of at most GAPP_MAX_TARGET residues go through gapped_profile_scores_kernel, which puts the
+// target in the rows and walks the profile's columns (its own comment below); longer ones through this kernel's PROFILE instantiations, whose image
+// builder reads the alignment profile instead of residues, composition bias and matrix.
 // Barriers: the matrix is staged before any loop; every barrier stands behind the loop whose LDS traffic it orders, with its own wait.
 // Selection kernel: ungapped_select_kernel's radix select and bitonic finish over int16 scores and the 47-bit key of mk_gapped.hpp, six histogram
 // passes at most (two over the score alone); the threshold and the query's e-value gate are applied as the scores are read.
@@ -71,7 +74,8 @@ struct Shape {
     static_assert(R % 4 == 0 && 256 % ROWS == 0, "a lane reads whole ds_read_b128; the image is built by 256 / ROWS threads per row");
 };
 
-template <int R>
+// PROFILE: the queries are profiles (V.p_aln); the image is filled from their columns and everything behind it is unchanged
+template <int R, bool PROFILE>
 __global__ __launch_bounds__(256) void gapped_scores_kernel(GappedView V, uint32_t p0, uint32_t a, uint32_t b, uint32_t nItemsPerPair, uint32_t nItems,
                                                             uint2 *park, uint64_t parkStride) {
     typedef Shape<R> S;
@@ -81,7 +85,7 @@ __global__ __launch_bounds__(256) void gapped_scores_kernel(GappedView V, uint32
     __shared__ int8_t sMat[21 * 21];
     __shared__ unsigned long long sWork[2];
     const uint32_t tid = threadIdx.x, sub = tid % G, grp = tid / G;
-    for (uint32_t k = tid; k < 21 * 21; k += 256) sMat[k] = V.mat[k];
+    if (!PROFILE) for (uint32_t k = tid; k < 21 * 21; k += 256) sMat[k] = V.mat[k];
     if (tid < 2) sWork[tid] = 0;
     __syncthreads();
     const v2s go2 = (v2s) (short) GAP_OPEN, ge2 = (v2s) (short) GAP_EXTEND, zero2 = (v2s) (short) 0;
@@ -112,13 +116,16 @@ __global__ __launch_bounds__(256) void gapped_scores_kernel(GappedView V, uint32
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     real[h] = gi < qLen[h];
-                    qc[h] = real[h] ? (int) min((uint32_t) V.q_res[qOff[h] + gi], 20u) : 0;
-                    cb[h] = real[h] ? (int) V.q_bias8[qOff[h] + gi] : 0;
+                    qc[h] = (!PROFILE && real[h]) ? (int) min((uint32_t) V.q_res[qOff[h] + gi], 20u) : 0;
+                    cb[h] = (!PROFILE && real[h]) ? (int) V.q_bias8[qOff[h] + gi] : 0;
                 }
                 for (uint32_t code = tid / ROWS; code <= (uint32_t) GAP_PAD_CODE; code += 256 / ROWS) {
                     int v[2];
 #pragma unroll
-                    for (int h = 0; h < 2; h++) v[h] = (real[h] && code < 21u) ? gapped_cell_score(sMat[code * 21 + qc[h]], cb[h]) : GAP_PAD;
+                    for (int h = 0; h < 2; h++) {
+                        if (PROFILE) v[h] = (real[h] && code < 21u) ? gapped_profile_score(V.p_aln + (qOff[h] + gi) * 32, (int) code) : GAP_PAD;
+                        else v[h] = (real[h] && code < 21u) ? gapped_cell_score(sMat[code * 21 + qc[h]], cb[h]) : GAP_PAD;
+                    }
                     sImg[(code * LINE) / 4 + row] = ((uint32_t) v[0] & 0xFFFFu) | ((uint32_t) v[1] << 16);
                 }
             }
@@ -193,6 +200,147 @@ __global__ __launch_bounds__(256) void gapped_scores_kernel(GappedView V, uint32
             if (tLen > 0 && gapped_pair_scored(V.cov_thr, V.cov_mode, ql, tLen)) {
                 score = (int) (short) (gm >> (16 * sub));
                 cells += (unsigned long long) ql * tLen;
+            }
+            V.scores[(size_t) row * V.ns + pos] = (int16_t) score;
+            bytes += 2 + (sub == 0 ? tLen : 0);
+        }
+    }
+    if (bytes) atomicAdd(&sWork[0], bytes);
+    if (cells) atomicAdd(&sWork[1], cells);
+    __syncthreads();
+    if (tid < 2 && sWork[tid]) atomicAdd(&V.work[tid], sWork[tid]);
+}
+
+// ---- profile queries, the target in the rows ----
+// A lane group owns one target of at most G x R residues, lane l its residues l R .. l R + R - 1 as rows; the steps are the profile's columns in
+// blocks of four, and at step kb lane l works on block kb - l: the block the lane above it finished one step earlier.  Inside a block a lane runs
+// row-major over its R x 4 cells.  Across blocks it carries E and the H of the block's last column per row (2 R registers); inside a block F per
+// column (4) and the row above's H over the block's columns plus the diagonal (5).  The bottom row's H[4] and F[4] travel to the next lane by
+// row_shr:1 once per block; no residue travels: the byte offset of a row's image line is computed once per target.
+// The image in LDS is [22 lines: 20 residues, X, the pad line][column][2 profiles] int16, so the four columns of a block for one residue are 16
+// aligned bytes: one ds_read_b128 per row and block, packed for both profiles of the register pair.  It is a window over the columns of WB steps and
+// the seven blocks of lane lag in front of them (image block i of window w = column block w WB + i - 7), refilled behind a barrier; columns in
+// front of column 0 and behind a profile's end hold GAP_PAD (mk_gapped.hpp: the padding argument, transposed).  The step count depends on the
+// profile pair only, so every group of a workgroup walks the same steps and the barriers stand in uniform control flow, each behind the loop
+// whose LDS traffic it orders.
+namespace prof {
+constexpr int CB = GAPP_BLOCK, LAGB = G - 1, WB = GAPP_WINDOW / CB, IBLK = WB + LAGB, ICOLS = IBLK * CB;
+constexpr int LINE = ICOLS * 4;                                    // bytes of an image line: a column is two int16
+constexpr int IMAGE = (GAP_PAD_CODE + 1) * LINE;
+static_assert(CB == 4 && LINE % 16 == 0, "a block of one line is one aligned ds_read_b128");
+static_assert(IMAGE <= 32 * 1024, "two workgroups and more per compute unit");
+}  // namespace prof
+
+template <int R>
+__global__ __launch_bounds__(256) void gapped_profile_scores_kernel(GappedView V, uint32_t a, uint32_t b, uint32_t nItemsPerPair, uint32_t nItems) {
+    using namespace prof;
+    __shared__ __attribute__((aligned(16))) uint32_t sImg[IMAGE / 4];
+    __shared__ unsigned long long sWork[2];
+    const uint32_t tid = threadIdx.x, sub = tid % G, grp = tid / G;
+    if (tid < 2) sWork[tid] = 0;
+    __syncthreads();
+    const v2s go2 = (v2s) (short) GAP_OPEN, ge2 = (v2s) (short) GAP_EXTEND, zero2 = (v2s) (short) 0;
+    const uint32_t nTB = (b - a + GROUPS - 1) / GROUPS;
+    unsigned long long bytes = 0, cells = 0;
+
+    for (uint32_t item = blockIdx.x; item < nItems; item += gridDim.x) {
+        const uint32_t pair = item / nItemsPerPair, tbg = item % nItemsPerPair;
+        // the two profiles of the pair (workgroup-uniform); an absent one has no columns
+        uint64_t pOff[2]; uint32_t pLen[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const uint32_t row = pair * 2 + h;
+            pOff[h] = 0; pLen[h] = 0;
+            if (row < V.nq) { const uint32_t qi = V.q_order[V.q0 + row]; pOff[h] = V.q_off[qi]; pLen[h] = (uint32_t) (V.q_off[qi + 1] - pOff[h]); }
+        }
+        const uint32_t lpMax = max(pLen[0], pLen[1]);
+        const uint32_t steps = lpMax ? (lpMax + CB - 1) / CB + LAGB : 0, nWin = (steps + WB - 1) / WB;
+
+#pragma unroll 1
+        for (int tb = 0; tb < GAP_BLOCKS_PER_WG; tb++) {
+            const uint32_t blk = tbg * GAP_BLOCKS_PER_WG + tb, pos = a + blk * GROUPS + grp;
+            const bool valid = blk < nTB && pos < b;
+            uint32_t tLen = 0; uint64_t tOff = 0;
+            if (valid) { const uint32_t tIdx = V.t_order[V.s0 + pos]; tOff = V.t_off[tIdx]; tLen = (uint32_t) (V.t_off[tIdx + 1] - tOff); }
+            // a pair that cannot be covered is not walked; the group walks when either profile of the register is to be scored (a target beyond the
+            // shape's rows is the caller's error and is left unscored)
+            const bool walk = valid && tLen > 0 && tLen <= (uint32_t) (G * R) && ((pLen[0] && gapped_pair_scored(V.cov_thr, V.cov_mode, pLen[0], tLen)) ||
+                                                                                  (pLen[1] && gapped_pair_scored(V.cov_thr, V.cov_mode, pLen[1], tLen)));
+            // the image lines of the lane's rows: fixed for the whole walk; a row behind the target's end reads the pad line
+            uint32_t line[R];
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const uint32_t i = sub * R + r;
+                line[r] = (walk && i < tLen ? min((uint32_t) V.t_res[tOff + i], 20u) : (uint32_t) GAP_PAD_CODE) * LINE;
+            }
+            v2s E[R], Hl[R], m = zero2, hDiag = zero2;                  // hDiag: the bottom row of the lane above in the column in front of the block
+#pragma unroll
+            for (int r = 0; r < R; r++) { E[r] = zero2; Hl[r] = zero2; }
+            uint32_t outH[CB] = {0, 0, 0, 0}, outF[CB] = {0, 0, 0, 0};
+
+            for (uint32_t w = 0; w < nWin; w++) {
+                if (tb == 0 || nWin > 1) {
+                    // the window's image: a thread takes one column of one profile, 32 bytes of it, and writes its 22 lines
+                    for (uint32_t k = tid; k < (uint32_t) ICOLS * 2; k += 256) {
+                        const uint32_t ic = k >> 1, h = k & 1;
+                        const int64_t col = (int64_t) w * (WB * CB) + ic - LAGB * CB;
+                        const bool real = col >= 0 && col < (int64_t) pLen[h];
+                        uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+                        if (real) { const uint4 *src = (const uint4 *) (V.p_aln + (pOff[h] + (uint64_t) col) * 32); lo = src[0]; hi = src[1]; }
+                        const uint32_t wds[5] = {lo.x, lo.y, lo.z, lo.w, hi.x};
+                        int16_t *dst = (int16_t *) sImg + ic * 2 + h;
+#pragma unroll
+                        for (int code = 0; code <= GAP_PAD_CODE; code++) {
+                            const int s = code < 20 ? (int) (int8_t) (wds[code >> 2] >> (8 * (code & 3))) : 0;      // (gapped_profile_score on the loaded bytes)
+                            dst[code * (LINE / 2)] = (int16_t) (real && code < 21 ? s : GAP_PAD);
+                        }
+                    }
+                }
+                workgroup_sync_lds();
+                if (walk) {
+                    const uint32_t k0 = w * WB, k1 = min(steps, k0 + WB);
+                    const char *mine = (const char *) sImg + (LAGB - sub) * 16;
+#pragma unroll 1
+                    for (uint32_t kb = k0; kb < k1; kb++) {
+                        v2s up[CB + 1], F[CB];
+                        up[0] = hDiag;
+#pragma unroll
+                        for (int c = 0; c < CB; c++) {
+                            up[c + 1] = as_v2s(from_above(0u, outH[c], sub));
+                            F[c] = as_v2s(from_above(0u, outF[c], sub));
+                        }
+                        hDiag = up[CB];
+                        const char *at = mine + (kb - k0) * 16;
+#pragma unroll
+                        for (int r = 0; r < R; r++) {
+                            const uint4 x = *(const uint4 *) (at + line[r]);
+                            const uint32_t sc[CB] = {x.x, x.y, x.z, x.w};
+                            v2s d = up[0], e = E[r];
+                            up[0] = Hl[r];
+#pragma unroll
+                            for (int c = 0; c < CB; c++) {
+                                const v2s h = gapped_cell<GapPk>(d, as_v2s(sc[c]), e, F[c], go2, ge2);
+                                d = up[c + 1]; up[c + 1] = h;
+                                m = GapPk::vmax(m, h);
+                            }
+                            Hl[r] = up[CB]; E[r] = e;
+                        }
+#pragma unroll
+                        for (int c = 0; c < CB; c++) { outH[c] = as_u32(up[c + 1]); outF[c] = as_u32(F[c]); }
+                    }
+                }
+                workgroup_sync_lds();                                 // the window is read out before the next one, target block or item overwrites it
+            }
+
+            const uint32_t gm = group_max(as_u32(m));
+            if (!valid || sub >= 2) continue;
+            const uint32_t row = pair * 2 + sub;                       // lane h of the group writes profile h of the register
+            if (row >= V.nq) continue;
+            const uint32_t pl = sub ? pLen[1] : pLen[0];
+            int score = 0;
+            if (walk && gapped_pair_scored(V.cov_thr, V.cov_mode, pl, tLen)) {
+                score = (int) (short) (gm >> (16 * sub));
+                cells += (unsigned long long) pl * tLen;
             }
             V.scores[(size_t) row * V.ns + pos] = (int16_t) score;
             bytes += 2 + (sub == 0 ? tLen : 0);
@@ -292,7 +440,8 @@ __global__ __launch_bounds__(256) void gapped_select_kernel(GappedView V, Gapped
 template <int R>
 void launch_shape(const GappedView &V, uint32_t p0, uint32_t a, uint32_t b, uint32_t perPair, uint32_t items, uint2 *park, uint64_t parkStride, uint32_t blocks,
                   hipStream_t stream) {
-    hipLaunchKernelGGL(gapped_scores_kernel<R>, dim3(blocks), dim3(256), 0, stream, V, p0, a, b, perPair, items, park, parkStride);
+    if (V.p_aln) hipLaunchKernelGGL((gapped_scores_kernel<R, true>), dim3(blocks), dim3(256), 0, stream, V, p0, a, b, perPair, items, park, parkStride);
+    else hipLaunchKernelGGL((gapped_scores_kernel<R, false>), dim3(blocks), dim3(256), 0, stream, V, p0, a, b, perPair, items, park, parkStride);
 }
 
 }  // namespace
@@ -310,6 +459,21 @@ hipError_t launch_gapped_scores(const GappedView &V, int shape, uint32_t p0, uin
         case 0: launch_shape<gapped_shape_rows(0)>(V, p0, a, b, perPair, (uint32_t) items, park, parkStride, blocks, stream); break;
         case 1: launch_shape<gapped_shape_rows(1)>(V, p0, a, b, perPair, (uint32_t) items, park, parkStride, blocks, stream); break;
         default: launch_shape<gapped_shape_rows(2)>(V, p0, a, b, perPair, (uint32_t) items, park, parkStride, blocks, stream); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_gapped_profile_scores(const GappedView &V, int shape, uint32_t a, uint32_t b, hipStream_t stream) {
+    if (b <= a || V.nq == 0) return hipSuccess;
+    if (b > V.ns || !V.p_aln || shape < 0 || shape >= GAP_SHAPES) return hipErrorInvalidValue;
+    const uint32_t nTB = (b - a + GROUPS - 1) / GROUPS, perPair = (nTB + GAP_BLOCKS_PER_WG - 1) / GAP_BLOCKS_PER_WG;
+    const uint64_t items = (uint64_t) perPair * ((V.nq + 1) / 2);
+    if (items > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t) items), block(256);
+    switch (shape) {
+        case 0: hipLaunchKernelGGL(gapped_profile_scores_kernel<gapped_shape_rows(0)>, grid, block, 0, stream, V, a, b, perPair, (uint32_t) items); break;
+        case 1: hipLaunchKernelGGL(gapped_profile_scores_kernel<gapped_shape_rows(1)>, grid, block, 0, stream, V, a, b, perPair, (uint32_t) items); break;
+        default: hipLaunchKernelGGL(gapped_profile_scores_kernel<gapped_shape_rows(2)>, grid, block, 0, stream, V, a, b, perPair, (uint32_t) items); break;
     }
     return hipGetLastError();
 }

@@ -18,6 +18,22 @@
 // is 0 or strictly below a real cell of the pair.  In a pad COLUMN behind the target the same holds with E coming from the real cell to the left; in
 // front of the target everything is 0.  A pad cell never raises the pair's maximum, and no real cell reads one: pad rows lie below, pad columns
 // outside.  (A pad row's H is also handed on as the diagonal term of the next pad row, where -32768 clears it again.)
+// Profile queries (the inverted search of a profile target database: ungappedprefilter.cpp:373-374 hands qSeq.getAlignmentProfile() to ssw_init,
+// StripedSmithWaterman.cpp:1228-1247): column i and residue a score P[i][a], the int8 alignment profile (entries 0..19 of the [column][32] array of
+// mk_profile.hpp); X and every code above it score 0 in every column; there is no composition bias; GAP_POS_SCORING is not defined, so the gap costs
+// are the uniform 11 / 1.  Cell, running maximum, cap, verdicts, order and cut are the ones above with the column count as the query length.
+// THE PADDING ARGUMENT, TRANSPOSED.  gapped_profile_scores_kernel puts the TARGET in the rows (8 lanes x R residues) and walks the profile's columns
+// in blocks of four, lane l one block behind lane l - 1.  Pad ROWS now lie behind a target's end (a target shorter than 8 R); pad COLUMNS lie in
+// front of column 0 (the lane lag: 7 blocks), behind the end of the shorter profile of a register pair, and behind the longer one's end (the
+// ramp-out and the rest of its last block).  gapped_cell is symmetric in E and F: exchanging rows and columns exchanges the two and nothing else, so
+// the argument above holds with the roles swapped, and written out it reads: a pad cell adds GAP_PAD, so it is max(E^, F^).  In a pad column in
+// FRONT of the profile every cell is 0: E and the H to the left start at 0, and the F that arrives from above was computed in the same column, a
+// pad column of the lane above (a lane works on the block the lane above it left one step earlier).  In a pad column BEHIND a profile's end F starts
+// at 0 at the top and is handed down inside the pad column, E comes from the real cell to the left, E = max(E_left - ge, H_left - go) < H_left: by
+// induction along the pad columns and down them every such cell is 0 or strictly below a real cell of the pair.  In a pad row E starts at 0 and
+// F comes down from the real cell above.  No real cell reads a pad cell: pad rows lie below the target, pad columns in front of column 0 hold zeros
+// (what the recurrence puts there anyway), and pad columns behind the end lie to the right of every real cell of that half.  The halves of a
+// register never mix, so the shorter profile's pad columns do not touch the longer one's cells.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -58,6 +74,9 @@ __host__ __device__ inline typename A::V gapped_cell(typename A::V diag, typenam
 // what a real cell adds: matrix entry + the row's composition bias (ssw_init's word profile, score bias 0)
 __host__ __device__ inline int gapped_cell_score(int matScore, int compBias) { return matScore + compBias; }
 
+// what column `col` ([32] int8, mk_profile.hpp) of a profile query scores for residue code `code`: X and every code above it score 0
+__host__ __device__ inline int gapped_profile_score(const int8_t *col, int code) { return code < 20 ? (int) col[code] : 0; }
+
 // the pair's verdict in front of the score (Util::canBeCovered) ...
 __host__ __device__ inline bool gapped_pair_scored(float covThr, int covMode, uint32_t qLen, uint32_t tLen) {
     return can_be_covered(covThr, covMode, (float) qLen, (float) tLen);
@@ -92,6 +111,28 @@ inline int gapped_pair_host(const int8_t *mat, const uint8_t *q, const int8_t *b
     return best;
 }
 
+// one (profile, target) pair, the same row loop over the profile's columns (the twin of the profile kernels).  aln32 = [nCols][32] int8
+inline int gapped_profile_pair_host(const int8_t *aln32, int nCols, const uint8_t *t, int tLen) {
+    if (tLen <= 0) return 0;
+    int *H = new int[2 * (size_t) tLen](), *F = H + tLen;
+    int best = 0;
+    for (int i = 0; i < nCols; i++) {
+        int diag = 0, E = 0;
+        for (int j = 0; j < tLen; j++) {
+            const int h = gapped_cell<GapInt>(diag, gapped_profile_score(aln32 + (size_t) i * 32, t[j]), E, F[j], GAP_OPEN, GAP_EXTEND);
+            diag = H[j]; H[j] = h;
+            best = h > best ? h : best;
+        }
+    }
+    delete[] H;
+    return best;
+}
+
+// the work split of gapped_profile_scores_kernel (mk_gapped.hip): the target in the rows (GAP_GROUP lanes x gapped_shape_rows), the profile's columns in
+// blocks of GAPP_BLOCK, lane l GAPP_BLOCK columns behind lane l - 1; the image in LDS holds the columns of GAPP_WINDOW / GAPP_BLOCK steps and the lag
+constexpr int GAPP_BLOCK = 4, GAPP_LAG = (GAP_GROUP - 1) * GAPP_BLOCK, GAPP_WINDOW = 256;
+constexpr int GAPP_MAX_TARGET = GAP_MAX_TILE;             // longer targets take the row-tiled kernel with the profile's columns as its rows
+
 // ---- the kernel side (mk_gapped.hip) ----
 struct GappedView {
     const uint8_t *q_res; const uint64_t *q_off; const int8_t *q_bias8; uint32_t n_queries;
@@ -105,6 +146,7 @@ struct GappedView {
     int16_t *scores;                           // [nq][ns] one int16 per pair, 0 for a skipped pair
     unsigned long long *work;                  // [0] algorithmic bytes, [1] cells
     const GateEntry *gate;                     // [query length] the e-value verdict per score; nullptr: no e-value test (the selection reads it)
+    const int8_t *p_aln = nullptr;             // profile queries: [column][32] alignment profile, q_off the column offsets (q_res, q_bias8, mat unused)
 };
 // the scores of the query pairs [p0, p1) of the chunk (pair p = rows 2 p and 2 p + 1) against positions [a, b) of the chunk's targets with tile
 // shape `shape`; every query of the range has at most GAP_GROUP x gapped_shape_rows(shape) residues, except with the last shape, which walks a
@@ -113,6 +155,9 @@ struct GappedView {
 // Shorter shapes take no park memory
 hipError_t launch_gapped_scores(const GappedView &V, int shape, uint32_t p0, uint32_t p1, uint32_t a, uint32_t b, uint2 *park, uint64_t parkStride,
                                 uint32_t blocks, hipStream_t stream);
+// profile queries (V.p_aln), the target in the rows: the scores of every profile pair of the chunk against positions [a, b) of the chunk's targets,
+// each of at most GAP_GROUP x gapped_shape_rows(shape) residues.  Longer targets go through launch_gapped_scores, which reads V.p_aln as well
+hipError_t launch_gapped_profile_scores(const GappedView &V, int shape, uint32_t a, uint32_t b, hipStream_t stream);
 // the best max_seqs hits of every query of the chunk over the chunk's targets and the candidates kept from earlier target chunks (the contract of
 // UngappedSelect, over gapped_hit_key)
 struct GappedSelect {
