@@ -143,6 +143,18 @@ int mk_result_filter(const mk_params *p, int q_len, int t_len, const mk_alignmen
  * reached max(qn, tn) without the score ("Alignment score and position are not consensus", where the reference exits). */
 int mk_backtrace_host(const int8_t *mat21x21, const uint8_t *q, const int8_t *q_bias8, int qn, const uint8_t *t, int tn, int score,
                       int gap_open, int gap_extend, char *ops, uint32_t ops_cap, uint32_t *bt_len, uint32_t *identities, uint32_t *attempts);
+/* the same for ONE profile query, host code without a GPU and without mk_init (the twin mk_profile_backtrace's kernel is checked against):
+ * SmithWaterman::banded_sw<PROFILE_SEQ> + computerBacktrace<SUBSTITUTIONMATRIX> (the instance every type but PROFILE_PROFILE takes,
+ * StripedSmithWaterman.cpp:533-537) on the columns q_start .. q_start + qn - 1 of a profile of n_cols_total columns and the tn residues t STARTS at.
+ * aln32 = the [n_cols_total][32] int8 alignment profile, letters = the query letters [n_cols_total], both as mk_profiles_derived reports them.
+ * Column q_start + i and residue code t[j] < 20 score aln32[(q_start + i) * 32 + t[j]]; X and every code above 20 score 0 (the rule of
+ * mk_gapped_prefilter_profile_host); there is no composition bias.  Gap costs are the uniform gap_open / gap_extend: PROFILE_SEQ is instantiated
+ * with posSpecificGaps = true, but the per-position arrays are only read under GAP_POS_SCORING, which the reference's build does not define.
+ * *identities = the M columns whose target residue equals letters[column] (profile->query_sequence is Sequence::numSequence, the query letters,
+ * not the consensus).  Bands, attempts, ops and return codes as for mk_backtrace_host; MK_ERR_ARG also for columns outside the profile. */
+int mk_backtrace_profile_host(const int8_t *aln32, const uint8_t *letters, int n_cols_total, int q_start, int qn,
+                              const uint8_t *t, int tn, int score, int gap_open, int gap_extend,
+                              char *ops, uint32_t ops_cap, uint32_t *bt_len, uint32_t *identities, uint32_t *attempts);
 
 /* ---- encoding: Sequence::mapSequence + SubstitutionMatrix::aa2num (Sequence.cpp:307-324) ---- */
 void mk_encode(const char *ascii, size_t len, uint8_t *codes);
@@ -274,6 +286,17 @@ int mk_align_limit_scan(const uint8_t *verdicts, const uint64_t *offsets, uint32
  * ops[ops_offsets[k] .. ops_offsets[k+1]), uncompressed M / I / D (empty for a pair without a path), and identities[k] identical residues.
  * Views owned by the batch handle.  MK_ERR_ARG when the batch was not aligned with add_backtrace. */
 int mk_align_backtrace(const mk_queries *q, const char **ops, const uint64_t **ops_offsets /* n_alignments + 1 */, const uint32_t **identities);
+/* the banded backtrace of PROFILE queries, a stage behind mk_align / mk_search on a profile batch (the way mk_alt_alignments runs behind them): every
+ * accepted record's rectangle [q_start, q_end] x [db_start, db_end] is traced with its raw_score (mk_backtrace_profile_host states the pair), its
+ * aln_len becomes the backtrace's length and its seq_id Util::computeSeqId(seq_id_mode, identities, q_len, db_len, aln_len).  The batch's backtrace
+ * result is filled: mk_align_backtrace returns the identities and, with keep_ops = 1, the operation strings; mk_format_alignment_bt prints the
+ * 11-column line.  A pair without a path keeps its aln_len and gets empty operations and 0 identities, as in mode 3.
+ * These are the backtraces of the records mode 2 kept, not a re-run of the criteria: the record set and the record order do not change (with
+ * --min-aln-len > 0 the reference's mode 3, which tests the backtrace's length, could keep a few records more).
+ * Roles as for mk_gapped_prefilter_profile -- a batch of mk_profiles_create, a database created with profile_search = 1, params->profile_search = 1 --
+ * anything else MK_ERR_UNSUPPORTED.  MK_ERR_ARG: seq_id_mode outside 0 .. 2, keep_ops outside 0 / 1, no alignment result on the batch, a record
+ * without start positions.  Of params, gap_open and gap_extend are read. */
+int mk_profile_backtrace(mk_targetdb *db, mk_queries *q, const mk_params *params, int seq_id_mode, int keep_ops);
 
 /* ---- rescorediagonal: the ungapped alignment of every prefilter hit on its diagonal (M/src/alignment/rescorediagonal.cpp:193-364,
  * DistanceCalculator.h:93-201), the stage `search --alignment-mode 4` runs in place of align (Search.cpp:261, 314-315, 387).  Reads the batch's

@@ -59,7 +59,8 @@ EXPORTS = ["mk_init", "mk_last_error", "mk_default_params", "mk_device_name", "m
            "mk_ungapped_prefilter", "mk_ungapped_prefilter_host", "mk_debug_ungapped_constants",
            "mk_ungapped_prefilter_profile_host", "mk_debug_ungapped_profile_constants",
            "mk_gapped_prefilter", "mk_gapped_prefilter_host", "mk_debug_gapped_constants",
-           "mk_gapped_prefilter_profile", "mk_gapped_prefilter_profile_host", "mk_debug_gapped_profile_constants"]
+           "mk_gapped_prefilter_profile", "mk_gapped_prefilter_profile_host", "mk_debug_gapped_profile_constants",
+           "mk_backtrace_profile_host", "mk_profile_backtrace"]
 
 
 def lib():
@@ -811,6 +812,36 @@ def backtrace_host(mat, q, bias8, t, score, gap_open=11, gap_extend=1):
     if rc < 0:
         _chk(rc)
     return (ops[:n.value].tobytes() if rc == 0 else None), int(ids.value), int(att.value)
+
+
+def backtrace_profile_host(aln32, letters, q_start, qn, t, score, gap_open=11, gap_extend=1):
+    """the backtrace of one profile query's rectangle, host code (mk_backtrace_profile_host): aln32 = int8 [cols, 32] and letters = uint8 [cols] of the
+    WHOLE profile as Profiles.derived() reports them, the rectangle = its columns q_start .. q_start + qn - 1 x the codes t -> as backtrace_host"""
+    aln32 = np.ascontiguousarray(aln32, dtype=np.int8); letters = np.ascontiguousarray(letters, dtype=np.uint8)
+    t = np.ascontiguousarray(t, dtype=np.uint8)
+    assert aln32.ndim == 2 and aln32.shape[1] == 32 and len(letters) == len(aln32)
+    ops = np.zeros(max(1, int(qn) + len(t)), dtype=np.uint8)
+    n, ids, att = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = lib().mk_backtrace_profile_host(_p(aln32), _p(letters), C.c_int(len(aln32)), C.c_int(int(q_start)), C.c_int(int(qn)), _p(t), C.c_int(len(t)),
+                                         C.c_int(int(score)), C.c_int(gap_open), C.c_int(gap_extend), _p(ops), C.c_uint32(ops.size), C.byref(n), C.byref(ids),
+                                         C.byref(att))
+    if rc < 0:
+        _chk(rc)
+    return (ops[:n.value].tobytes() if rc == 0 else None), int(ids.value), int(att.value)
+
+
+# columns of the largest LDS image of the profile backtrace kernel (csrc/mk_trace.hpp: TRACE_PROF_IMG_COLS; a run with a wider window reads the profile
+# from global memory and is counted under the kernel statistic "trace_profile_global" -- tests/test_gpu_profile_backtrace.py holds the two together)
+PROFILE_TRACE_IMAGE_COLS = 2816
+
+
+def profile_backtrace(db, q, params=None, seq_id_mode=0, keep_ops=True):
+    """the banded backtrace of a profile batch's accepted records, behind align / search (mk_profile_backtrace): aln_len and seq_id of the batch's
+    alignment result are rewritten -> (alignments, offsets) as align_result and (ops bytes, ops offsets, identities) as align_backtrace"""
+    p = params or db.params
+    _chk(lib().mk_profile_backtrace(db.h, q.h, C.byref(p), C.c_int(int(seq_id_mode)), C.c_int(int(keep_ops))))
+    alns, aoff = align_result(q)
+    return (alns, aoff), align_backtrace(q, int(aoff[-1]))
 
 
 def sw_backtrace_pairs(db, q, q_idx, t_idx, in5, params=None, keep_ops=True):

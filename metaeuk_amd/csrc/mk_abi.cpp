@@ -604,6 +604,23 @@ int mk_backtrace_host(const int8_t *mat, const uint8_t *q, const int8_t *bias8, 
     return st == mk::TRACE_OK ? MK_OK : 1;
 }
 
+int mk_backtrace_profile_host(const int8_t *aln32, const uint8_t *letters, int nColsTotal, int qStart, int qn, const uint8_t *t, int tn, int score,
+                              int gapOpen, int gapExtend, char *ops, uint32_t opsCap, uint32_t *btLen, uint32_t *identities, uint32_t *attempts) {
+    if (!aln32 || !letters || !t || qn <= 0 || tn <= 0) return fail(MK_ERR_ARG, "mk_backtrace_profile_host: null argument or empty rectangle");
+    if (qStart < 0 || (int64_t) qStart + qn > (int64_t) nColsTotal)
+        return fail(MK_ERR_ARG, "mk_backtrace_profile_host: columns %d .. %lld outside the profile's %d", qStart, (long long) qStart + qn - 1, nColsTotal);
+    if (ops && (uint64_t) opsCap < (uint64_t) qn + (uint64_t) tn)
+        return fail(MK_ERR_ARG, "mk_backtrace_profile_host: ops_cap %u below qn + tn = %llu", opsCap, (unsigned long long) qn + (unsigned long long) tn);
+    mk::TraceResult r;
+    const int st = mk::trace_profile_host(aln32 + (size_t) qStart * 32, letters + qStart, qn, t, tn, score, gapOpen, gapExtend, ops, opsCap, &r);
+    if (btLen) *btLen = r.bt_len;
+    if (identities) *identities = r.identities;
+    if (attempts) *attempts = r.attempts;
+    if (st == mk::TRACE_STALLED)
+        return fail(MK_ERR_SW_MISMATCH, "Alignment score and position are not consensus: a %d x %d rectangle misses its score %d at band %d", qn, tn, score, r.band);
+    return st == mk::TRACE_OK ? MK_OK : 1;
+}
+
 int mk_result_filter(const mk_params *p, int q_len, int t_len, const mk_alignment *a) {
     if (!p) return fail(MK_ERR_ARG, "null argument");
     int rc = check_filters(p, false);
@@ -1499,6 +1516,64 @@ int mk_sw_backtrace_pairs(mk_targetdb *db, mk_queries *q, const mk_params *P, co
         if (finalBand) finalBand[p] = res[k].band;
         if (ops && res[k].bt_len) std::memcpy(ops + opsOff[p], buf.data() + off[k], res[k].bt_len);
     }
+    return MK_OK;
+}
+
+// the backtraces of a profile batch's accepted records (mk_trace.hip: trace_profile_kernel), a stage behind mk_align / mk_search
+int mk_profile_backtrace(mk_targetdb *db, mk_queries *q, const mk_params *P, int seqIdMode, int keepOps) {
+    int rc = ensure_ready();
+    if (rc) return rc;
+    if (!db || !q || !P) return fail(MK_ERR_ARG, "null argument");
+    if (!q->isProfile || !db->profileSearch || P->profile_search == 0)
+        return fail(MK_ERR_UNSUPPORTED, "mk_profile_backtrace takes profile queries as the inverted search does: a profile batch, a target database created with "
+                                        "profile_search = 1 and params->profile_search = 1 (batch: %s, database: %d, params: %d)",
+                    q->isProfile ? "profiles" : "sequences", db->profileSearch ? 1 : 0, P->profile_search);
+    if (seqIdMode < 0 || seqIdMode > 2) return fail(MK_ERR_ARG, "--seq-id-mode %d out of range (0 to 2)", seqIdMode);
+    if (keepOps != 0 && keepOps != 1) return fail(MK_ERR_ARG, "mk_profile_backtrace: keep_ops %d out of range (0 or 1)", keepOps);
+    if (!q->haveAln) return fail(MK_ERR_ARG, "mk_profile_backtrace: the batch has no alignment result");
+    const size_t n = (size_t) q->alnOff[q->n];
+    mk_alignment *alns = (mk_alignment *) q->alns.p;
+    std::vector<mk::TracePair> pairs(n);
+    std::vector<uint32_t> owner(n);
+    std::vector<uint64_t> off(n + 1, 0);
+    for (uint32_t i = 0; i < q->n; i++) {
+        const int64_t qLen = (int64_t) (q->off[i + 1] - q->off[i]);
+        for (uint64_t k = q->alnOff[i]; k < q->alnOff[i + 1]; k++) {
+            const mk_alignment &a = alns[k];
+            if (a.db_key >= db->n) return fail(MK_ERR_ARG, "mk_profile_backtrace: alignment %llu names target %u outside the database", (unsigned long long) k, a.db_key);
+            const int64_t tLen = (int64_t) (db->off[a.db_key + 1] - db->off[a.db_key]);
+            if (a.q_start < 0 || a.q_end < a.q_start || a.q_end >= qLen || a.db_start < 0 || a.db_end < a.db_start || a.db_end >= tLen || a.raw_score <= 0)
+                return fail(MK_ERR_ARG, "mk_profile_backtrace: alignment %llu carries no rectangle inside its pair (columns %d .. %d of %lld, residues %d .. %d of %lld, score %d)",
+                            (unsigned long long) k, a.q_start, a.q_end, (long long) qLen, a.db_start, a.db_end, (long long) tLen, a.raw_score);
+            mk::TracePair &tp = pairs[k];
+            tp.q_pos = q->off[i] + (uint64_t) a.q_start; tp.t_pos = db->off[a.db_key] + (uint64_t) a.db_start;
+            tp.qn = a.q_end - a.q_start + 1; tp.tn = a.db_end - a.db_start + 1; tp.score = a.raw_score;
+            owner[k] = i;
+            off[k + 1] = off[k] + (keepOps ? (uint64_t) tp.qn + (uint64_t) tp.tn : 0);
+        }
+    }
+    std::vector<mk::TraceResult> res(n);
+    std::vector<char> buf(off[n]);
+    std::string err;
+    mk::TraceStageStats st;
+    const mk::TraceProfile prof{q->dProfAln.p, owner.data()};
+    rc = mk::run_trace_device(q->dRes.p, nullptr, db->dRes.p, nullptr, pairs.data(), n, P->gap_open, P->gap_extend, keepOps == 1, off.data(), buf.data(), g_stream,
+                              res.data(), err, timed_begin, timed_end, &st, &prof);
+    timed_flush();
+    if (rc != MK_OK) return fail(rc, "%s", err.c_str());
+    // Matcher.cpp:105-113 as mode 3 applies it: the backtrace's length when there is a path, the exact identity
+    q->btOps.clear(); q->btIds.assign(n, 0); q->btOff.assign(n + 1, 0);
+    for (size_t k = 0; k < n; k++) {
+        const bool path = res[k].status == mk::TRACE_OK && res[k].bt_len > 0;
+        mk_alignment &a = alns[k];
+        if (path) a.aln_len = (int32_t) res[k].bt_len;
+        a.seq_id = mk::compute_seq_id(seqIdMode, path ? (int) res[k].identities : 0, a.q_len, a.db_len, a.aln_len);
+        q->btIds[k] = path ? res[k].identities : 0u;
+        if (path && keepOps) q->btOps.insert(q->btOps.end(), buf.begin() + (ptrdiff_t) off[k], buf.begin() + (ptrdiff_t) (off[k] + res[k].bt_len));
+        q->btOff[k + 1] = q->btOps.size();
+    }
+    q->btLeftBand = st.leftBand;
+    q->haveBt = true;
     return MK_OK;
 }
 

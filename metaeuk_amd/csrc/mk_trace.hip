@@ -6,6 +6,8 @@
 // [k][lane] (ds_read_b32 / ds_write_b32 bank = lane % 32 whatever k a lane is at: conflict-free); wide groups keep them in global scratch
 // with the same interleaving.  Directions (four bits per cell, eight cells per word) go to global scratch as [word][lane]: the lanes of a wave
 // write neighbouring words.
+// Profile queries (mk_profile_backtrace) go through trace_profile_kernel: the same lane walk behind another scorer, the jobs grouped by profile
+// and the profile's columns staged once per workgroup (its own comment below, and mk_trace.hpp).
 #include "mk_trace.hpp"
 #include "mk_kernels.hpp"
 #include "../../include/metaeuk_amd.h"
@@ -13,6 +15,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <numeric>
 
 namespace mk {
@@ -20,6 +23,37 @@ namespace mk {
 namespace {
 
 constexpr uint64_t MK_TRACE_MAX_LEN = 1ull << 17;       // longest sequence of the library (mk_abi.cpp: MK_MAX_SEQ_LEN)
+
+// the three rolling rows of group g's lane for a job of `width` ints; false when they do not hold it (never: the host sized and classed them)
+__device__ inline bool lane_rows(const TraceLaunch &L, int32_t *sRows, uint32_t g, uint32_t lane, uint64_t width, Strided<int32_t> &hb, Strided<int32_t> &eb,
+                                 Strided<int32_t> &hc) {
+    if (L.lds_width == 0) {
+        // the group's rows are laid out for its widest job: three blocks of (widest x lanes) ints
+        const uint64_t widest = (L.row_base[g + 1] - L.row_base[g]) / (3ull * L.lanes);
+        if (width > widest) return false;
+        int32_t *base = L.rows + L.row_base[g] + lane;
+        hb = Strided<int32_t>{base, L.lanes}; eb = Strided<int32_t>{base + widest * L.lanes, L.lanes}; hc = Strided<int32_t>{base + 2 * widest * L.lanes, L.lanes};
+    } else {
+        const uint32_t w = L.lds_width;
+        if (width > w) return false;
+        const uint32_t ln = L.lanes;
+        hb = Strided<int32_t>{sRows + lane, ln}; eb = Strided<int32_t>{sRows + w * ln + lane, ln}; hc = Strided<int32_t>{sRows + 2 * w * ln + lane, ln};
+    }
+    return true;
+}
+
+// one job behind its scorer: the attempt at the job's band and, when it reaches the score, the trace (q = the letters identities are counted with)
+template <class Scorer>
+__device__ inline void lane_job(const TraceLaunch &L, const TraceJob &J, const Scorer &S, uint32_t g, uint32_t lane, Strided<int32_t> hb, Strided<int32_t> eb,
+                                Strided<int32_t> hc) {
+    const Strided<uint32_t> dir{L.dirs + L.dir_base[g] + lane, L.lanes};
+    const uint8_t *q = L.q_res + J.q_pos, *t = L.t_res + J.t_pos;
+    const int32_t max = banded_fill(S, J.qn, t, J.tn, L.gap_open, L.gap_extend, J.band, hb, eb, hc, dir);
+    TraceOut o{0, 0, TRACE_MISSED, 0};
+    if (max >= J.score)
+        o.status = banded_trace(q, J.qn, t, J.tn, J.band, dir, L.ops + J.ops_end, L.write_ops != 0, (uint32_t) (J.qn + J.tn), &o.bt_len, &o.identities);
+    L.out[J.slot] = o;
+}
 
 __global__ __launch_bounds__(64) void trace_kernel(TraceLaunch L) {
     __shared__ int8_t sMat[21 * 21 + 3];
@@ -30,27 +64,38 @@ __global__ __launch_bounds__(64) void trace_kernel(TraceLaunch L) {
     const uint64_t id = (uint64_t) g * L.lanes + lane;
     if (lane >= L.lanes || id >= L.n_jobs) return;
     const TraceJob J = L.jobs[id];
-    const uint64_t width = trace_row_ints(J.band);
     Strided<int32_t> hb, eb, hc;
-    if (L.lds_width == 0) {
-        // the group's rows are laid out for its widest job: three blocks of (widest x lanes) ints
-        const uint64_t widest = (L.row_base[g + 1] - L.row_base[g]) / (3ull * L.lanes);
-        if (width > widest) { L.out[J.slot] = TraceOut{0, 0, TRACE_STALLED, 0}; return; }       // (never: the host sized them)
-        int32_t *base = L.rows + L.row_base[g] + lane;
-        hb = Strided<int32_t>{base, L.lanes}; eb = Strided<int32_t>{base + widest * L.lanes, L.lanes}; hc = Strided<int32_t>{base + 2 * widest * L.lanes, L.lanes};
-    } else {
-        const uint32_t w = L.lds_width;
-        if (width > w) { L.out[J.slot] = TraceOut{0, 0, TRACE_STALLED, 0}; return; }            // (never: the host classed them)
-        const uint32_t ln = L.lanes;
-        hb = Strided<int32_t>{sRows + lane, ln}; eb = Strided<int32_t>{sRows + w * ln + lane, ln}; hc = Strided<int32_t>{sRows + 2 * w * ln + lane, ln};
+    if (!lane_rows(L, sRows, g, lane, trace_row_ints(J.band), hb, eb, hc)) { L.out[J.slot] = TraceOut{0, 0, TRACE_STALLED, 0}; return; }
+    lane_job(L, J, SeqScorer{sMat, L.q_res + J.q_pos, L.q_bias8 + J.q_pos}, g, lane, hb, eb, hc);
+}
+
+// Profile queries: workgroup g = one run of TraceGroup (up to `lanes` jobs of ONE profile, a lane each).  IMG: the run's window of the profile
+// is staged into LDS behind the rolling rows, eight dwords of a column to nine (mk_trace.hpp), once for all the run's jobs; a lane's scorer
+// then starts at its own first column inside the image.  !IMG: a window beyond the launch's image -- the columns are read where they lie.
+// The staging loop is followed by its barrier in straight-line code (one wave per workgroup; the wait is the barrier's own).
+template <bool IMG>
+__global__ __launch_bounds__(64) void trace_profile_kernel(TraceLaunch L) {
+    extern __shared__ int32_t sRows[];                       // the rows of the class (as in trace_kernel), then the image
+    const uint32_t lane = threadIdx.x, g = blockIdx.x;
+    const TraceGroup G = L.groups[g];
+    int8_t *sImg = reinterpret_cast<int8_t *>(sRows + (size_t) 3 * L.lds_width * L.lanes);
+    const bool imgFits = G.win_cols <= L.img_cols;
+    if (IMG) {
+        if (imgFits) {
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(L.p_aln + G.win_pos * 32ull);
+            uint32_t *dst = reinterpret_cast<uint32_t *>(sImg);
+            for (uint32_t k = lane; k < G.win_cols * 8u; k += 64u) dst[(k >> 3) * (TRACE_PROF_COL_STRIDE / 4u) + (k & 7u)] = src[k];
+        }
+        __syncthreads();
     }
-    const Strided<uint32_t> dir{L.dirs + L.dir_base[g] + lane, L.lanes};
-    const uint8_t *q = L.q_res + J.q_pos, *t = L.t_res + J.t_pos;
-    const int32_t max = banded_fill(sMat, q, L.q_bias8 + J.q_pos, J.qn, t, J.tn, L.gap_open, L.gap_extend, J.band, hb, eb, hc, dir);
-    TraceOut o{0, 0, TRACE_MISSED, 0};
-    if (max >= J.score)
-        o.status = banded_trace(q, J.qn, t, J.tn, J.band, dir, L.ops + J.ops_end, L.write_ops != 0, (uint32_t) (J.qn + J.tn), &o.bt_len, &o.identities);
-    L.out[J.slot] = o;
+    if (lane >= L.lanes || lane >= G.n_jobs || (uint64_t) G.job_first + lane >= L.n_jobs) return;
+    const TraceJob J = L.jobs[G.job_first + lane];
+    Strided<int32_t> hb, eb, hc;
+    // (never: the host sized the rows, classed the jobs, and laid the window over every job of the run)
+    const bool inWindow = J.q_pos >= G.win_pos && J.q_pos + (uint64_t) J.qn <= G.win_pos + G.win_cols;
+    if (!lane_rows(L, sRows, g, lane, trace_row_ints(J.band), hb, eb, hc) || !inWindow || (IMG && !imgFits)) { L.out[J.slot] = TraceOut{0, 0, TRACE_STALLED, 0}; return; }
+    if (IMG) lane_job(L, J, ProfileScorer{sImg + (J.q_pos - G.win_pos) * TRACE_PROF_COL_STRIDE, TRACE_PROF_COL_STRIDE}, g, lane, hb, eb, hc);
+    else lane_job(L, J, ProfileScorer{L.p_aln + J.q_pos * 32ull, 32u}, g, lane, hb, eb, hc);
 }
 
 }  // namespace
@@ -63,8 +108,29 @@ hipError_t launch_trace(const TraceLaunch &L, hipStream_t stream) {
     return hipGetLastError();
 }
 
-int trace_host(const int8_t *mat, const uint8_t *q, const int8_t *bias8, int qn, const uint8_t *t, int tn, int score, int gapOpen, int gapExtend,
-               char *ops, uint32_t opsCap, TraceResult *res) {
+// the profile kernel: dynamic LDS = the class's rows + the launch's image (the image instantiation may ask for more than the default 64 KB)
+hipError_t launch_trace_profile(const TraceLaunch &L, uint32_t nGroups, hipStream_t stream) {
+    if (nGroups == 0) return hipSuccess;
+    const size_t rowBytes = (size_t) L.lds_width * 3 * L.lanes * sizeof(int32_t);
+    if (L.lds_width > (uint32_t) TRACE_LDS_WIDTH || L.lanes == 0 || L.lanes > 64 || rowBytes > 60000 || L.img_cols > TRACE_PROF_IMG_COLS || !L.p_aln || !L.groups)
+        return hipErrorInvalidValue;
+    const size_t lds = rowBytes + (size_t) L.img_cols * TRACE_PROF_COL_STRIDE;
+    constexpr int ldsMost = 60000 + (int) (TRACE_PROF_IMG_COLS * TRACE_PROF_COL_STRIDE);
+    static_assert(ldsMost <= 160 * 1024, "rows + image beyond the LDS of a gfx950 workgroup");
+    static std::once_flag once;
+    static hipError_t attrErr = hipSuccess;
+    std::call_once(once, [&] { attrErr = hipFuncSetAttribute(reinterpret_cast<const void *>(&trace_profile_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsMost); });
+    if (attrErr != hipSuccess) return attrErr;
+    if (L.img_cols > 0) hipLaunchKernelGGL(trace_profile_kernel<true>, dim3(nGroups), dim3(64), lds, stream, L);
+    else hipLaunchKernelGGL(trace_profile_kernel<false>, dim3(nGroups), dim3(64), rowBytes, stream, L);
+    return hipGetLastError();
+}
+
+namespace {
+// banded_sw's do-loop on the host: the attempts of one rectangle behind its scorer (q = the letters identities are counted with)
+template <class Scorer>
+int trace_host_with(const Scorer &S, const uint8_t *q, int qn, const uint8_t *t, int tn, int score, int gapOpen, int gapExtend, char *ops, uint32_t opsCap,
+                    TraceResult *res) {
     *res = TraceResult{0, 0, 0, TRACE_STALLED, 0};
     if (qn <= 0 || tn <= 0) return TRACE_STALLED;
     std::vector<int32_t> rows;
@@ -77,7 +143,7 @@ int trace_host(const int8_t *mat, const uint8_t *q, const int8_t *bias8, int qn,
         res->attempts++; res->band = band;
         const Strided<int32_t> hb{rows.data(), 1}, eb{rows.data() + w, 1}, hc{rows.data() + 2 * w, 1};
         const Strided<uint32_t> dir{dirs.data(), 1};
-        const int32_t max = banded_fill(mat, q, bias8, qn, t, tn, gapOpen, gapExtend, band, hb, eb, hc, dir);
+        const int32_t max = banded_fill(S, qn, t, tn, gapOpen, gapExtend, band, hb, eb, hc, dir);
         if (max >= score) {
             back.assign((size_t) qn + (size_t) tn, 0);
             res->status = banded_trace(q, qn, t, tn, band, dir, back.data() + back.size(), true, (uint32_t) back.size(), &res->bt_len, &res->identities);
@@ -90,12 +156,22 @@ int trace_host(const int8_t *mat, const uint8_t *q, const int8_t *bias8, int qn,
         if (band >= std::max(qn, tn)) return res->status = TRACE_STALLED;
     }
 }
+}  // namespace
+
+int trace_host(const int8_t *mat, const uint8_t *q, const int8_t *bias8, int qn, const uint8_t *t, int tn, int score, int gapOpen, int gapExtend,
+               char *ops, uint32_t opsCap, TraceResult *res) {
+    return trace_host_with(SeqScorer{mat, q, bias8}, q, qn, t, tn, score, gapOpen, gapExtend, ops, opsCap, res);
+}
+int trace_profile_host(const int8_t *cols, const uint8_t *letters, int qn, const uint8_t *t, int tn, int score, int gapOpen, int gapExtend,
+                       char *ops, uint32_t opsCap, TraceResult *res) {
+    return trace_host_with(ProfileScorer{cols, 32u}, letters, qn, t, tn, score, gapOpen, gapExtend, ops, opsCap, res);
+}
 
 #define TCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return MK_ERR_DEVICE; } } while (0)
 
 int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t *dTRes, const int8_t *dMat, const TracePair *pairs, size_t n,
                      int gapOpen, int gapExtend, bool keepOps, const uint64_t *opsOff, char *ops, hipStream_t stream, TraceResult *res,
-                     std::string &err, trace_timed_begin_fn tb, trace_timed_end_fn te, TraceStageStats *stats) {
+                     std::string &err, trace_timed_begin_fn tb, trace_timed_end_fn te, TraceStageStats *stats, const TraceProfile *prof) {
     if (n == 0) return MK_OK;
     if (n >= (1ull << 32)) { err = "backtrace stage: more than 2^32 pairs in one call"; return MK_ERR_UNSUPPORTED; }
     std::vector<uint32_t> pending(n);
@@ -108,6 +184,7 @@ int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t 
     std::vector<Item> cls[TRACE_NCLASS];
     std::vector<TraceJob> jobs;
     std::vector<uint64_t> dirBase, rowBase;
+    std::vector<TraceGroup> groups;                          // profile queries: the runs of a launch
     std::vector<TraceOut> outs;
     std::vector<char> opsBack;
     while (!pending.empty()) {
@@ -124,7 +201,16 @@ int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t 
             const bool wide = trace_class_width(c) == 0;
             std::vector<Item> &items = cls[c];
             // lanes of a group finish together: by work, then by pair (a fixed order: the launches of a call do not depend on anything else)
-            std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.dirBytes != b.dirBytes ? a.dirBytes < b.dirBytes : a.pair < b.pair; });
+            // profile queries: by profile first -- a group is a run of one profile's jobs and ends where the next profile begins
+            std::sort(items.begin(), items.end(), [&](const Item &a, const Item &b) {
+                if (prof && prof->owner[a.pair] != prof->owner[b.pair]) return prof->owner[a.pair] < prof->owner[b.pair];
+                return a.dirBytes != b.dirBytes ? a.dirBytes < b.dirBytes : a.pair < b.pair;
+            });
+            const auto group_end = [&](size_t lo, uint32_t ln) {
+                size_t hi = std::min(items.size(), lo + ln);
+                if (prof) { size_t k = lo + 1; while (k < hi && prof->owner[items[k].pair] == prof->owner[items[lo].pair]) k++; hi = k; }
+                return hi;
+            };
             size_t at = 0;
             while (at < items.size()) {
                 // one launch: groups of `lanes` jobs while the scratch stays under TRACE_SLICE_BYTES
@@ -142,7 +228,7 @@ int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t 
                 };
                 {
                     uint64_t d, r, o;
-                    const size_t hi = std::min(items.size(), at + lanes);
+                    const size_t hi = group_end(at, lanes);
                     if (group_bytes(at, hi, lanes, &d, &r, &o) > TRACE_SLICE_BYTES) {
                         // a pair too large to interleave with 63 others: on its own, one lane, stride 1
                         if (!wide) { err = "backtrace stage: internal error (a narrow group beyond the slice)"; return MK_ERR_DEVICE; }     // (never: `fits`)
@@ -158,16 +244,30 @@ int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t 
                         }
                     }
                 }
-                jobs.clear(); dirBase.clear(); rowBase.clear();
+                jobs.clear(); dirBase.clear(); rowBase.clear(); groups.clear();
                 uint64_t dirTotal = 0, rowTotal = 0, opsTotal = 0, used = 0;
+                uint32_t imgCols = 0;                                                 // profile queries: the launch's image = its largest window
+                bool imgLaunch = true;                                                // ... or none: a launch of runs whose windows exceed the capacity
                 double cells = 0;
                 const size_t first = at;
                 while (at < items.size()) {
-                    const size_t hi = std::min(items.size(), at + lanes);
+                    const size_t hi = group_end(at, lanes);
                     uint64_t d, r, o;
                     const uint64_t gb = group_bytes(at, hi, lanes, &d, &r, &o);
                     if (!jobs.empty() && used + gb > TRACE_SLICE_BYTES) break;
                     if (jobs.empty() && gb > TRACE_SLICE_BYTES) break;               // (the next launch decides: one lane per group)
+                    if (prof) {
+                        uint64_t lo = ~0ull, end = 0;                                 // the run's window: the union of its jobs' columns
+                        for (size_t k = at; k < hi; k++) {
+                            const TracePair &P = pairs[items[k].pair];
+                            lo = std::min(lo, P.q_pos); end = std::max(end, P.q_pos + (uint64_t) P.qn);
+                        }
+                        const bool fits = end - lo <= (uint64_t) TRACE_PROF_IMG_COLS;
+                        if (!jobs.empty() && fits != imgLaunch) break;               // (the other instantiation: the next launch)
+                        imgLaunch = fits;
+                        if (fits) imgCols = std::max(imgCols, (uint32_t) (end - lo));
+                        groups.push_back(TraceGroup{lo, (uint32_t) std::min<uint64_t>(end - lo, 0xFFFFFFFFull), (uint32_t) jobs.size(), (uint32_t) (hi - at), 0});
+                    }
                     dirBase.push_back(dirTotal / 4); rowBase.push_back(rowTotal);
                     for (size_t k = at; k < hi; k++) {
                         const uint32_t p = items[k].pair;
@@ -192,7 +292,9 @@ int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t 
                 uint32_t *dDirs = (uint32_t *) dev_scratch("trace_dirs", std::max<uint64_t>(dirTotal, 4));
                 int32_t *dRows = (int32_t *) dev_scratch("trace_rows", std::max<uint64_t>(rowTotal, 1) * sizeof(int32_t));
                 char *dOps = (char *) dev_scratch("trace_ops", std::max<uint64_t>(opsTotal, 1));
-                if (!dJobs || !dOut || !dBase || !dDirs || !dRows || !dOps) { err = "backtrace stage: device allocation failed"; return MK_ERR_DEVICE; }
+                TraceGroup *dGroups = prof ? (TraceGroup *) dev_scratch("trace_groups", ng * sizeof(TraceGroup)) : nullptr;
+                if (!dJobs || !dOut || !dBase || !dDirs || !dRows || !dOps || (prof && !dGroups)) { err = "backtrace stage: device allocation failed"; return MK_ERR_DEVICE; }
+                if (prof) TCHK(hipMemcpyAsync(dGroups, groups.data(), ng * sizeof(TraceGroup), hipMemcpyHostToDevice, stream));
                 TCHK(hipMemcpyAsync(dJobs, jobs.data(), nj * sizeof(TraceJob), hipMemcpyHostToDevice, stream));
                 TCHK(hipMemcpyAsync(dBase, dirBase.data(), ng * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
                 TCHK(hipMemcpyAsync(dBase + ng, rowBase.data(), (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
@@ -204,8 +306,10 @@ int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t 
                 L.ops = dOps; L.write_ops = keepOps ? 1u : 0u;
                 L.gap_open = gapOpen; L.gap_extend = gapExtend;
                 static const char *const names[TRACE_NCLASS] = {"sw_trace_lds11", "sw_trace_lds23", "sw_trace_lds67", "sw_trace_lds259", "sw_trace_lds1027", "sw_trace_global"};
-                const int th = tb ? tb(names[c], (double) dirTotal + (double) nj * (sizeof(TraceJob) + sizeof(TraceOut)), cells) : -1;
-                TCHK(launch_trace(L, stream));
+                if (prof) { L.p_aln = prof->dAln; L.groups = dGroups; L.img_cols = imgLaunch ? imgCols : 0; }
+                const char *name = prof ? (imgLaunch ? "trace_profile" : "trace_profile_global") : names[c];
+                const int th = tb ? tb(name, (double) dirTotal + (double) nj * (sizeof(TraceJob) + sizeof(TraceOut)), cells) : -1;
+                TCHK(prof ? launch_trace_profile(L, (uint32_t) ng, stream) : launch_trace(L, stream));
                 if (te) te(th);
                 outs.resize(nj);
                 TCHK(hipMemcpyAsync(outs.data(), dOut, nj * sizeof(TraceOut), hipMemcpyDeviceToHost, stream));

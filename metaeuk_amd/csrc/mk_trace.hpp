@@ -2,6 +2,9 @@
 // (mk_backtrace_host, the host assembly of the alignment stage) and the kernel of mk_trace.hip.
 // SmithWaterman::banded_sw<SEQ_SEQ> (M/src/alignment/StripedSmithWaterman.cpp:1347-1600) on the rectangle [q_start..q_end] x [t_start..t_end] of
 // a pair whose score and coordinates are known, then computerBacktrace<SUBSTITUTIONMATRIX> (:547-581) and Util::computeSeqId (Util.cpp:532-542).
+// banded_sw<PROFILE_SEQ> (profile queries: mk_backtrace_profile_host, mk_profile_backtrace) is the same code with another score lookup
+// (ProfileScorer below); computerBacktrace<SUBSTITUTIONMATRIX> is the instance it takes too (:533-537: only PROFILE_PROFILE takes the other),
+// and the letter it compares with the target residue is profile->query_sequence = Sequence::numSequence, the profile's query letters.
 // Kept from the reference: the first band |tn - qn| + 1, the whole DP redone with the band doubled while max < score, the three rolling
 // rows h_b / e_b / h_c in BAND coordinates with their edge cells set to 0 at every row (including the cell the `edge` index names when the
 // band is wider than the target, which is a cell of the previous row), the first row opening with -gap_open / -gap_extend, the strict
@@ -51,6 +54,28 @@ __host__ __device__ inline uint64_t trace_row_words(int band) { return (2ull * (
 __host__ __device__ inline uint64_t trace_dir_bytes(int qn, int band) { return (uint64_t) qn * trace_row_words(band) * 4ull; }
 __host__ __device__ inline uint64_t trace_row_ints(int band) { return 2ull * (uint64_t) band + 3ull; }
 
+// The score lookup, the one line in which banded_sw's branches differ (StripedSmithWaterman.cpp:1472-1477).  A scorer hands out what a row of
+// the rectangle scores with (row(i): loaded one row ahead) and the score of a target code in that row.
+// SEQ_SEQ: mat[q[i] * 21 + t[j]] + compositionBias[i].
+struct SeqScorer {
+    const int8_t *mat; const uint8_t *q; const int8_t *bias8;         // q / bias8 at the rectangle's first row
+    struct Row { uint32_t at; int32_t bias; };                        // (offsets, not pointers: `mat` keeps its address space through the loop)
+    __host__ __device__ inline Row row(int i) const { return Row{(uint32_t) q[i] * 21u, (int32_t) bias8[i]}; }
+    __host__ __device__ inline int32_t score(const Row &r, uint32_t t) const { return (int32_t) mat[r.at + t] + r.bias; }
+};
+// PROFILE_SEQ: mat[t[j] * qry_n + queryStart + i], here column (q_start + i) of the int8 alignment profile, cols[i * stride + t[j]] for the
+// residue codes 0 .. 19; X and every code above 20 score 0 (the rule of mk_gapped_prefilter_profile_host); no composition bias (banded_sw's
+// PROFILE_SEQ branch does not read it).  stride = 32 bytes in global memory, TRACE_PROF_COL_STRIDE in the LDS image of the profile kernel.
+// The gap costs stay the uniform ones: PROFILE_SEQ is instantiated with posSpecificGaps = true, but every use of gDelOpen / gDelClose / gIns
+// stands behind #ifdef GAP_POS_SCORING, which no build file of the reference defines -- banded_sw subtracts gap_open / gap_extend (11 / 1) as the
+// forward passes do.
+struct ProfileScorer {
+    const int8_t *cols; uint32_t stride;                              // cols at the rectangle's first column
+    struct Row { uint32_t at; };
+    __host__ __device__ inline Row row(int i) const { return Row{(uint32_t) i * stride}; }
+    __host__ __device__ inline int32_t score(const Row &r, uint32_t t) const { const int32_t v = cols[r.at + (t < 20u ? t : 19u)]; return t < 20u ? v : 0; }
+};
+
 // one attempt of banded_sw's do-loop body: fills `dir`, returns max.  hb / eb / hc hold trace_row_ints(band) ints each.
 // The band indices of the reference's set_u: a cell (i, j) is u = j - x + 1 of its own row (x = max(i - band, 0)) and e = j - xp + 1 of the
 // row above (xp = max(i - 1 - band, 0)); its left neighbour is b = u - 1 and its diagonal neighbour d = e - 1.  So h_c[b] is the H this lane
@@ -62,8 +87,8 @@ __host__ __device__ inline uint64_t trace_row_ints(int band) { return 2ull * (ui
 // with that row's query residue and bias) are loaded while this block is computed, the eight scores of a block are looked up together -- a lane
 // walks its cells alone, so every load left inside a cell would be paid in full, cell after cell.  (Indices past the row's end are clamped to
 // the rectangle's last column and never used.)
-template <class Rows, class Dirs>
-__host__ __device__ inline int32_t banded_fill(const int8_t *mat, const uint8_t *q, const int8_t *bias8, int qn, const uint8_t *t, int tn,
+template <class Scorer, class Rows, class Dirs>
+__host__ __device__ inline int32_t banded_fill(const Scorer &S, int qn, const uint8_t *t, int tn,
                                                int gapOpen, int gapExtend, int band, Rows hb, Rows eb, Rows hc, Dirs dir) {
     const int64_t width = (int64_t) band * 2 + 3;
     const uint64_t rowWords = trace_row_words(band);
@@ -72,8 +97,7 @@ __host__ __device__ inline int32_t banded_fill(const int8_t *mat, const uint8_t 
     uint32_t rowT[8];                                                 // residues of the first block of row i
 #pragma unroll
     for (int k = 0; k < 8; k++) rowT[k] = t[k < tn - 1 ? k : tn - 1];
-    uint32_t qc = q[0];
-    int32_t bias = bias8[0];
+    typename Scorer::Row row = S.row(0);
     for (int i = 0; i < qn; i++) {
         int beg = 0, end = tn - 1, u = 0;
         int j = i - band; beg = beg > j ? beg : j;
@@ -81,20 +105,19 @@ __host__ __device__ inline int32_t banded_fill(const int8_t *mat, const uint8_t 
         const int64_t edge = end + 1 < width - 1 ? end + 1 : width - 1;
         int32_t f = 0;
         hb[0] = 0; eb[0] = 0; hb[edge] = 0; eb[edge] = 0; hc[0] = 0;
-        uint32_t nextT[8], qcN = 0;
-        int32_t biasN = 0;
+        uint32_t nextT[8];
+        typename Scorer::Row rowN = row;                              // (the last row: nobody reads it)
         if (i + 1 < qn) {
             const int begN = i + 1 - band > 0 ? i + 1 - band : 0;
 #pragma unroll
             for (int k = 0; k < 8; k++) nextT[k] = t[begN + k < tn - 1 ? begN + k : tn - 1];
-            qcN = q[i + 1]; biasN = bias8[i + 1];
+            rowN = S.row(i + 1);
         } else {
 #pragma unroll
             for (int k = 0; k < 8; k++) nextT[k] = 0;
         }
         uint64_t word = rowWords * (uint64_t) i;                      // (i, beg) is column 0 of the row's directions: beg == x
         uint32_t acc = 0, col = 0;
-        const int8_t *mrow = mat + (int) qc * 21;
         const int x = i - band > 0 ? i - band : 0, xp = i - 1 - band > 0 ? i - 1 - band : 0;
         int32_t hLeft = 0;                                            // h_c[b] of the first cell: h_c[0]
         int32_t hDiag = hb[(size_t) (beg - xp)];                      // h_b[d] of the first cell
@@ -108,7 +131,7 @@ __host__ __device__ inline int32_t banded_fill(const int8_t *mat, const uint8_t 
 #pragma unroll
             for (int k = 0; k < 8; k++) tbN[k] = t[j0 + 8 + k < end ? j0 + 8 + k : end];
 #pragma unroll
-            for (int k = 0; k < 8; k++) sc[k] = (int32_t) mrow[tb[k]] + bias;
+            for (int k = 0; k < 8; k++) sc[k] = S.score(row, tb[k]);
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 j = j0 + k;
@@ -146,7 +169,7 @@ __host__ __device__ inline int32_t banded_fill(const int8_t *mat, const uint8_t 
         for (j = 1; j <= u; j++) hb[(size_t) j] = hc[(size_t) j];
 #pragma unroll
         for (int k = 0; k < 8; k++) rowT[k] = nextT[k];
-        qc = qcN; bias = biasN;
+        row = rowN;
     }
     return max;
 }
@@ -205,6 +228,20 @@ struct TraceOut { uint32_t bt_len, identities; int32_t status; int32_t pad; };
 // one class: lds_width > 0 -- every job has 2 * band + 3 <= lds_width and the three rolling rows are per-lane LDS columns (11 ints: band <= 4,
 // 8 KB of LDS per workgroup of 64 lanes; 23: band <= 10, 17 KB; 67: band <= 32, 50 KB; 259: band <= 128, 16 lanes, 49 KB; 1027: band <= 512, 4
 // lanes, 48 KB); lds_width == 0 -- the rows in global scratch: group g's three rows at row_base[g] ints into `rows` (row_base has a closing entry).
+// Profile queries turn the shape round: one profile owns hundreds of alignments.  There the jobs of a class are grouped BY PROFILE: a workgroup
+// takes a run of up to `lanes` jobs of one profile (a profile with more gets several workgroups) and stages the union of their column ranges --
+// the run's window, win_cols columns from column win_pos of the batch -- into LDS once, behind the class's rolling rows.  A column's 32 bytes
+// are laid TRACE_PROF_COL_STRIDE = 36 bytes apart: the lanes of a wave stand in different columns and read the byte their target code selects,
+// and with the natural stride of 32 bytes (8 banks) every fourth column would start in the same bank; 9 dwords are coprime to the bank count, so
+// 32 consecutive columns start in 32 different banks.  TRACE_PROF_IMG_COLS columns (99 KB) is the largest image: with the 50 KB of the widest
+// row class it stays under the 160 KB of a gfx950 workgroup.  A launch allocates the largest window of its runs, not the capacity (a profile of
+// 300 columns costs 11 KB and leaves the CU to other workgroups).  A run whose window is larger is launched through the kernel's second
+// instantiation, which reads the columns from global memory (stride 32).
+constexpr uint32_t TRACE_PROF_COL_STRIDE = 36;
+constexpr uint32_t TRACE_PROF_IMG_COLS = 2816;
+static_assert(TRACE_PROF_COL_STRIDE >= 32 && TRACE_PROF_COL_STRIDE % 4 == 0 && (TRACE_PROF_COL_STRIDE / 4) % 2 == 1,
+              "a column is staged as 8 dwords, and its stride in dwords must be odd to be coprime to the bank count");
+struct TraceGroup { uint64_t win_pos; uint32_t win_cols, job_first, n_jobs, pad; };
 constexpr int TRACE_NCLASS = 6;
 constexpr int TRACE_LDS_WIDTH = 1027;
 __host__ __device__ inline int trace_class_width(int c) { const int w[TRACE_NCLASS] = {11, 23, 67, 259, 1027, 0}; return w[c]; }
@@ -218,8 +255,13 @@ struct TraceLaunch {
     const uint64_t *row_base; int32_t *rows;       // wide launch only
     char *ops; uint32_t write_ops;
     int gap_open, gap_extend;
+    // profile queries (trace_profile_kernel): q_res = the query letters, q_bias8 / mat unused
+    const int8_t *p_aln = nullptr;               // [column][32] int8 alignment profile of the batch
+    const TraceGroup *groups = nullptr;          // one per workgroup
+    uint32_t img_cols = 0;                       // columns of the LDS image of this launch (0: the profile is read from global memory)
 };
 hipError_t launch_trace(const TraceLaunch &L, hipStream_t stream);
+hipError_t launch_trace_profile(const TraceLaunch &L, uint32_t nGroups, hipStream_t stream);
 
 // ---- the stage: every rectangle through the kernel, band by band ----
 // A rectangle starts at q_res[q_pos] / t_res[t_pos] (device arrays) and has qn x tn cells; score = the pair's Smith-Waterman score.
@@ -230,16 +272,24 @@ constexpr uint64_t TRACE_SLICE_BYTES = 512ull << 20;
 struct TraceStageStats { double cells = 0; uint64_t launches = 0, jobs[TRACE_NCLASS] = {0, 0, 0, 0, 0, 0}, leftBand = 0; };
 typedef int (*trace_timed_begin_fn)(const char *name, double bytes, double cells);
 typedef void (*trace_timed_end_fn)(int handle);
+// prof: the rectangles of profile queries through trace_profile_kernel (kernel statistics "trace_profile", and "trace_profile_global" for the
+// launches that read the profile from global memory).  q_pos counts COLUMNS of the batch, dQRes = the query letters, dQBias8 / dMat are not read;
+// dAln = the batch's [column][32] alignment profile (device), owner[p] = the profile pair p belongs to (host): the groups of a launch are runs
+// of one owner.  Rounds, slices, attempts and results are the same.
+struct TraceProfile { const int8_t *dAln; const uint32_t *owner; };
 // Rounds: all pairs at their first band; those that miss the score again with the band doubled (one readback per launch).  keepOps: the
 // operation strings, pair p's at ops[opsOff[p] .. opsOff[p] + res[p].bt_len) with opsOff[p + 1] - opsOff[p] >= qn + tn (host arrays).
 // MK_OK, MK_ERR_SW_MISMATCH (a stalled band), MK_ERR_UNSUPPORTED (a pair beyond TRACE_SLICE_BYTES), MK_ERR_DEVICE.
 int run_trace_device(const uint8_t *dQRes, const int8_t *dQBias8, const uint8_t *dTRes, const int8_t *dMat, const TracePair *pairs, size_t n,
                      int gapOpen, int gapExtend, bool keepOps, const uint64_t *opsOff, char *ops, hipStream_t stream, TraceResult *res,
-                     std::string &err, trace_timed_begin_fn tb, trace_timed_end_fn te, TraceStageStats *stats = nullptr);
+                     std::string &err, trace_timed_begin_fn tb, trace_timed_end_fn te, TraceStageStats *stats = nullptr, const TraceProfile *prof = nullptr);
 // the same pair on the host: banded_sw + computerBacktrace as one call (pointers at the rectangle's first residues).  ops (may be null)
 // receives the string from ops[0]; opsCap >= qn + tn.
 int trace_host(const int8_t *mat, const uint8_t *q, const int8_t *bias8, int qn, const uint8_t *t, int tn, int score, int gapOpen, int gapExtend,
                char *ops, uint32_t opsCap, TraceResult *res);
+// the same for a profile query: cols = the [column][32] alignment profile at the rectangle's first column, letters = the query letters there
+int trace_profile_host(const int8_t *cols, const uint8_t *letters, int qn, const uint8_t *t, int tn, int score, int gapOpen, int gapExtend,
+                       char *ops, uint32_t opsCap, TraceResult *res);
 
 
 }  // namespace mk
