@@ -689,6 +689,7 @@ struct AlignShapes {
     uint32_t unitsPerBlock = 0;              // MK_SW_UNITS_PER_BLOCK: short-lived workgroups instead of the persistent launch
     int knownForce = -1, knownWaves = 12;
     bool fwdLargeFirst = false;              // MK_SW_FWD_LARGE_FIRST=1
+    bool fwdFine = true;                     // MK_SW_FINE=0: the score pass without the 80- / 112-row bodies (mk_sw.hip: swp_kernel)
     bool multiLargeFirst = true;             // MK_SW_MULTI_LARGE_FIRST=0: the register classes of the position / reverse passes small tiles first
     bool multiPrio = true;                   // MK_SW_MULTI_PRIO=0: the persistent position / reverse workgroups do not ask for issue priority
     uint32_t multiPerCu[3] = {24, 12, 12};   // MK_SW_MULTI_WAVES: one-wave workgroups per CU of the three register classes (<= 64, 96 .. 256, >= 384 rows)
@@ -724,6 +725,7 @@ static const AlignShapes &align_shapes() {
         S.multiPrio = knob_long("MK_SW_MULTI_PRIO", 1) != 0;
         S.fwdLargeFirst = knob_long("MK_SW_FWD_LARGE_FIRST", 0) != 0;
         S.multiLargeFirst = knob_long("MK_SW_MULTI_LARGE_FIRST", 1) != 0;
+        S.fwdFine = knob_long("MK_SW_FINE", 1) != 0;
         if (const char *e = knob("MK_SW_MULTI_WAVES")) {
             int k = 0;
             for (const char *p = e; *p && k < 3; k++) { S.multiPerCu[k] = (uint32_t) std::max(1, atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; }
@@ -911,6 +913,7 @@ static int run_shared_fwd(const AlignView &V, const mk_params &P, const uint64_t
         L.work_counter = dWork + c; L.work_counter_t = dWork + 16 + c; L.persistent_blocks = S.persistentBlocks[c]; L.units_per_block = S.unitsPerBlock;
         L.gap_open = P.gap_open; L.gap_extend = P.gap_extend;
         L.narrow = narrow;
+        L.fine = S.fwdFine;
         // the transposed score pass: profile queries, the 32-lane tiles (512 / 768 rows; on the 16-lane tiles the classic layout already ramps over 15
         // steps only and wins: 5 -> 10, 12 -> 17, 54 -> 58 ms at 192 / 256 / 384 rows, profiles/r06_transposed_score_pass.txt)
         {

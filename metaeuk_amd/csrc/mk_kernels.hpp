@@ -44,6 +44,8 @@ struct SwLaunch {
     const int32_t *known_score; // position / reverse pass: the maximum score of job j is known_score[jobs[j].slot] (launch_sw_known needs it; launch_sw, per-job
                                 // profiles, stops a DP once that score has been seen in a finished column; null: unknown)
     bool narrow = false;        // score pass: the 16-lane variant of the 384-row tile (the waves were cut with sw_cfg_jobs_per_wave(c, true))
+    bool fine = true;           // score pass: 80- / 112-row bodies inside the 96- / 128-row launches (sequence queries);
+                                // false: the launch's own rows per lane always
 };
 
 // tile configurations: G lanes per DP x R rows per lane; a job uses the smallest one whose G*R >= q_len

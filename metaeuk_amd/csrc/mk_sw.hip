@@ -675,25 +675,181 @@ __global__ __launch_bounds__(64) void swt_kernel(SwLaunch L) {
     }
 }
 
-// R rows per lane; the LDS profile keeps RP >= R (even) int16 slots per lane so that a lane's scores are whole dwords.
-// G = 16 lanes per pair of DPs for tiles of at most 256 rows; G = 32 for 384 / 512 rows, where diag + score can pass 32767
-// and the add saturates like the reference's word pass (simdi16_adds, StripedSmithWaterman.cpp:1059).
-template <int R, int RP = R, int G = 16>
-__global__ __launch_bounds__(64) void swp_kernel(SwLaunch L) {
-    constexpr int GPB = 64 / G, ROWS = G * RP;
+// One round of a wave: the profile of the wave's query, the column loop, the reduction, the bound and the store.  The LDS layout is that of the
+// kernel's launch (ROWS = G * RP slots per profile row); R <= RP rows of every lane are real.  A launch may run bodies of different R over
+// the same RP: each builds its own profile, since the row of a slot depends on R.
+template <int R, int RP, int G>
+__device__ __forceinline__ void swp_wave(const SwLaunch &L, int8_t *smem, const uint32_t w0, const uint32_t count, const pk16 go2, const pk16 ge2) {
+    constexpr int ROWS = G * RP;
     constexpr bool SAT = G * R * 127 > 32767;
     static_assert(RP >= R && RP % 2 == 0, "profile slots per lane: even and at least R");
-    static_assert(G == 16 || G == 32, "a pair of DPs runs on one or two DPP rows");
-    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int16_t *prof = reinterpret_cast<int16_t *>(smem);            // prof[t][row], int16; row 21 = zeros
-    // behind the profile: the substitution matrix (loaded once per persistent wave) and the query's residues / composition bias of the
-    // current unit -- the profile is then built from LDS, two global loads per lane instead of a dependent pair per profile entry
     int8_t *sMat = smem + (size_t) 22 * ROWS * sizeof(int16_t);
     uint8_t *sQ = reinterpret_cast<uint8_t *>(sMat + 448);
     int8_t *sB = reinterpret_cast<int8_t *>(sQ + ROWS);
+    int tid = (int) threadIdx.x;
+    // (opaque to the compiler: what a body derives from the thread index -- slot numbers of the profile build, LDS addresses -- is computed per round
+    //  and not hoisted out of the persistent loop, where it stays in registers beside the other body's.  AMD clang 22.0.0git (ROCm 7.2.0), VGPRs
+    //  without / with it: <6,6,16> 71 / 63, <8,8,16> 78 / 69, <16,16,16> 119 / 107, <24,24,32> 135 / 122; 75, 80, 105 and 131 before
+    //  swp_wave.  A later compiler may not need it; it costs a handful of integer instructions per round.)
+    asm volatile("" : "+v"(tid));
+    const int lane = tid % G, grp = tid / G;
+    const pk16 zero2 = pk_splat(0);
+    // (the jobs are loaded here, not in the kernel: loaded in front of a choice between two bodies, all their fields stay in registers
+    //  through the body)
+    const bool haveA = (uint32_t) (2 * grp) < count, haveB = (uint32_t) (2 * grp + 1) < count;
+    const SwJob jobA = L.jobs[L.order[(uint64_t) w0 + (haveA ? 2 * grp : 0)]];
+    const SwJob jobB = L.jobs[L.order[(uint64_t) w0 + (haveB ? 2 * grp + 1 : 0)]];
+    const int qLen = (int) jobA.q_len;                          // every job of the wave has this query
+    const int tLenA = haveA ? (int) jobA.t_len : 0, tLenB = haveB ? (int) jobB.t_len : 0;
+    if (L.q_prof) {
+        // profile query: the row's scores are its own column of the alignment profile (see sw_unit)
+        for (int i = tid; i < ROWS * 6; i += 64) {
+            const int slot = i / 6, w = i - slot * 6;
+            const int row = RP == R ? slot : (slot / RP) * R + slot % RP;
+            const bool real = row < qLen && (RP == R || slot % RP < R);
+            uint32_t v = 0;
+            if (real) v = *reinterpret_cast<const uint32_t *>(L.q_prof + ((int64_t) jobA.q_start + (int64_t) row * jobA.q_step) * 32 + w * 4);
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (4 * w + k < 22) prof[(4 * w + k) * ROWS + slot] = (int16_t) (int8_t) (v >> (8 * k));
+        }
+    } else {
+    for (int slot = tid; slot < ROWS; slot += 64) {
+        const int row = RP == R ? slot : (slot / RP) * R + slot % RP;    // lane-major: lane * R + r
+        const bool real = row < qLen && (RP == R || slot % RP < R);
+        const int64_t qi = (int64_t) jobA.q_start + (int64_t) (real ? row : 0) * jobA.q_step;
+        sQ[slot] = real ? L.q_res[qi] : (uint8_t) 255;
+        sB[slot] = real ? L.q_bias8[qi] : (int8_t) 0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int idx = tid; idx < 22 * ROWS; idx += 64) {
+        const int t = idx / ROWS, slot = idx - t * ROWS;
+        const uint32_t qc = sQ[slot];
+        prof[idx] = (t < 21 && qc != 255u) ? (int16_t) ((int) sMat[t * 21 + (int) qc] + (int) sB[slot]) : (int16_t) 0;
+    }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    pk16 H[R], E[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) { H[r] = zero2; E[r] = zero2; }
+    pk16 best = zero2, hupPrev = zero2;
+    int roseA = 0, roseB = 0;                                  // first step of the block of 16 in which this lane's running maximum last rose
+    // what travels with a column is not the two residues but the byte offsets of their profile rows (residue * ROWS * 2, code 21 =
+    // "no column": an all-zero row), packed in one dword and prepared when the column is fetched -- nothing per step
+    constexpr uint32_t ROWB = (uint32_t) ROWS * 2u, NOCOL = 21u * ROWB | (21u * ROWB) << 16;
+    uint32_t outH = 0, outF = 0, outRes = NOCOL;              // handed to lane+1: H of the last row, F, the two profile-row offsets
+    const int tMax = max(tLenA, tLenB);
+    // whole blocks of 16 steps (the steps past the last column see all-zero profile rows, which cannot raise the maximum): the
+    // block is unrolled, so the lane-to-lane hand-over needs no register copies and no loop control
+    // (a last block of 8 steps was measured and not kept: 0.4 % fewer instructions, a step the benchmark cannot tell from the spread of its
+    // runs -- profiles/score_pass_padding.txt)
+    const int steps = tMax > 0 ? (tMax + G - 1 + 15) & ~15 : 0;
+    const int laneRow = lane & 15;                             // position in the DPP row (both rows of a 32-lane group fetch the same residues)
+    const int lastA = max(tLenA - 1, 0), lastB = max(tLenB - 1, 0);
+    const int64_t baseA = (int64_t) jobA.t_start, baseB = (int64_t) jobB.t_start, stepA = jobA.t_step, stepB = jobB.t_step;
+    const auto fetch = [&](int col) -> uint32_t {
+        const uint32_t ra = col < tLenA ? (uint32_t) L.t_res[baseA + (int64_t) min(col, lastA) * stepA] : 21u;
+        const uint32_t rb = col < tLenB ? (uint32_t) L.t_res[baseB + (int64_t) min(col, lastB) * stepB] : 21u;
+        return ra * ROWB | (rb * ROWB) << 16;
+    };
+    const char *profLane = reinterpret_cast<const char *>(prof + lane * RP);
+    // the residues of a block of 16 steps are fetched three blocks ahead: the loads have ~3 x 16 steps to land, which also covers the
+    // memory latency of a chip whose HBM the prefilter of the other stream keeps saturated
+    uint32_t tq0 = fetch(laneRow), tq1 = fetch(16 + laneRow), tq2 = fetch(32 + laneRow);
+    for (int s0 = 0; s0 < steps; s0 += 16) {
+        uint32_t tcur = tq0;
+        tq0 = tq1; tq1 = tq2;
+        tq2 = fetch(s0 + 48 + laneRow);
+        const uint32_t bestIn = pk_bits(best);
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const uint32_t top = tcur;
+            tcur = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) tcur, 0x12F /* row_ror:15 */, 0xf, 0xf, false);
+            const pk16 hup = pk_from(shift_up_zero<G>(outH, lane));
+            pk16 F = pk_from(shift_up_zero<G>(outF, lane));
+            const uint32_t tres = shift_up<G>(top, outRes, lane);
+            const int16_t *pa = reinterpret_cast<const int16_t *>(profLane + (tres & 0xFFFFu)), *pb = reinterpret_cast<const int16_t *>(profLane + (tres >> 16));
+            uint32_t wa[RP / 2], wb[RP / 2];                   // R int16 scores per target, two per dword
+            if constexpr (RP % 4 == 0) {
+                // a lane's RP scores are RP * 2 bytes at a multiple of 8: read as 64-bit words.  As dwords (ds_read2_b32) the lanes of a group sit on
+                // every second bank and two groups share a cycle: 3.0 conflict cycles per active LDS cycle in the 48- / 64-row tiles
+                // (profiles/r06_contention.txt)
+                const uint64_t *qa = reinterpret_cast<const uint64_t *>(__builtin_assume_aligned(pa, 8)), *qb = reinterpret_cast<const uint64_t *>(__builtin_assume_aligned(pb, 8));
+#pragma unroll
+                for (int k = 0; k < RP / 4; k++) {
+                    const uint64_t xa = qa[k], xb = qb[k];
+                    wa[2 * k] = (uint32_t) xa; wa[2 * k + 1] = (uint32_t) (xa >> 32); wb[2 * k] = (uint32_t) xb; wb[2 * k + 1] = (uint32_t) (xb >> 32);
+                }
+            } else {
+#pragma unroll
+            for (int k = 0; k < RP / 2; k++) { wa[k] = reinterpret_cast<const uint32_t *>(pa)[k]; wb[k] = reinterpret_cast<const uint32_t *>(pb)[k]; }
+            }
+            pk16 dsave = hupPrev;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                // (score of target A, score of target B) for row r: one byte permute
+                const pk16 sc = pk_from(__builtin_amdgcn_perm(wb[r / 2], wa[r / 2], (r & 1) ? 0x07060302u : 0x05040100u));
+                const pk16 d = SAT ? __builtin_elementwise_add_sat(dsave, sc) : dsave + sc;
+                dsave = H[r];
+                const pk16 h = pk_max(pk_max(d, E[r]), F);         // E, F >= 0 (clamped subtractions) keep H non-negative
+                best = pk_max(best, h);
+                const pk16 ho = pk_subs0(h, go2);
+                E[r] = pk_max(pk_subs0(E[r], ge2), ho);
+                F = pk_max(pk_subs0(F, ge2), ho);
+                H[r] = h;
+            }
+            hupPrev = hup;
+            outH = pk_bits(H[R - 1]);
+            outF = pk_bits(F);
+            outRes = tres;
+        }
+        const uint32_t rose = pk_bits(best) ^ bestIn;
+        if (rose & 0xFFFFu) roseA = s0;
+        if (rose >> 16) roseB = s0;
+    }
+    // group reduction of the two maxima
+    uint32_t b = pk_bits(best);
+#pragma unroll
+    for (int m = G / 2; m >= 1; m >>= 1) b = pk_bits(pk_max(pk_from(b), pk_from((uint32_t) __shfl_xor((int) b, m, G))));
+    // ... and a bound for the position pass: a lane whose rows hold the maximum reached it in the block of steps in which its running
+    // maximum last rose, i.e. in a column <= that block's last step - lane; the first column that reaches the maximum (what the position
+    // pass reports) is not beyond the smallest such bound, so the position pass may stop there (the columns behind it cannot change its answer)
+    uint32_t cA = (pk_bits(best) & 0xFFFFu) == (b & 0xFFFFu) ? (uint32_t) max(roseA + 15 - lane, 0) : 0x7FFFFFFFu;
+    uint32_t cB = (pk_bits(best) >> 16) == (b >> 16) ? (uint32_t) max(roseB + 15 - lane, 0) : 0x7FFFFFFFu;
+#pragma unroll
+    for (int m = G / 2; m >= 1; m >>= 1) {
+        cA = min(cA, (uint32_t) __shfl_xor((int) cA, m, G));
+        cB = min(cB, (uint32_t) __shfl_xor((int) cB, m, G));
+    }
+    if (lane == 0) {
+        SwOut o;
+        o.end_row = -1; o.pad = 0;                              // end_col: not the end cell's column but a bound for it (gate_emit_kernel cuts the position job there)
+        if (haveA) { o.score = (int32_t) (int16_t) (b & 0xFFFFu); o.end_col = (int32_t) min(cA, (uint32_t) lastA); L.out[jobA.slot] = o; }
+        if (haveB) { o.score = (int32_t) (int16_t) (b >> 16); o.end_col = (int32_t) min(cB, (uint32_t) lastB); L.out[jobB.slot] = o; }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// R rows per lane; the LDS profile keeps RP >= R (even) int16 slots per lane so that a lane's scores are whole dwords.
+// G = 16 lanes per pair of DPs for tiles of at most 256 rows; G = 32 for 384 / 512 rows, where diag + score can pass 32767
+// and the add saturates like the reference's word pass (simdi16_adds, StripedSmithWaterman.cpp:1059).
+// The 96- and 128-row tiles, sequence queries (L.fine): a wave whose query fits G * RF rows, RF = R - 1, runs the body of RF rows per lane in
+// the same LDS layout -- 80 rows instead of 96, 112 instead of 128
+template <int R, int RP = R, int G = 16>
+__global__ __launch_bounds__(64) void swp_kernel(SwLaunch L) {
+    constexpr int GPB = 64 / G, ROWS = G * RP;
+    constexpr int RF = (G == 16 && RP == R && (R == 6 || R == 8)) ? R - 1 : R;
+    static_assert(G == 16 || G == 32, "a pair of DPs runs on one or two DPP rows");
+    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
+    // behind the profile: the substitution matrix (loaded once per persistent wave) and the query's residues / composition bias of the
+    // current unit -- the profile is then built from LDS, two global loads per lane instead of a dependent pair per profile entry
+    int8_t *sMat = smem + (size_t) 22 * ROWS * sizeof(int16_t);
     for (int k = (int) threadIdx.x; k < 441; k += 64) sMat[k] = L.mat[k];
-    const int lane = threadIdx.x % G, grp = threadIdx.x / G;
-    const pk16 go2 = pk_splat(L.gap_open), ge2 = pk_splat(L.gap_extend), zero2 = pk_splat(0);
+    const pk16 go2 = pk_splat(L.gap_open), ge2 = pk_splat(L.gap_extend);
     for (uint32_t done = 0; L.units_per_block == 0 || done < L.units_per_block; done++) {
         uint32_t u = 0;
         if (threadIdx.x == 0) u = atomicAdd(L.work_counter, 1u);
@@ -703,142 +859,13 @@ __global__ __launch_bounds__(64) void swp_kernel(SwLaunch L) {
         // profile queries (L.narrow: their waves hold up to 8 jobs whatever the tile): the transposed unit takes the wave unless a fragment is long
         if (L.t_max_rows && swt_longest(L, wFirst, min(8u, wEnd - wFirst)) <= L.t_max_rows) continue;       // swt_kernel's
         for (uint32_t w0 = wFirst; w0 < wEnd; w0 += (uint32_t) (2 * GPB)) {          // (a wave of 8 jobs on a 32-lane tile: two rounds of 4)
-        const uint32_t w1 = wEnd;
-        const uint32_t count = min((uint32_t) (2 * GPB), w1 - w0);
-        const bool haveA = (uint32_t) (2 * grp) < count, haveB = (uint32_t) (2 * grp + 1) < count;
-        const SwJob jobA = L.jobs[L.order[(uint64_t) w0 + (haveA ? 2 * grp : 0)]];
-        const SwJob jobB = L.jobs[L.order[(uint64_t) w0 + (haveB ? 2 * grp + 1 : 0)]];
-        const int qLen = (int) jobA.q_len;                          // every job of the wave has this query
-        const int tLenA = haveA ? (int) jobA.t_len : 0, tLenB = haveB ? (int) jobB.t_len : 0;
-        if (L.q_prof) {
-            // profile query: the row's scores are its own column of the alignment profile (see sw_unit)
-            for (int i = (int) threadIdx.x; i < ROWS * 6; i += 64) {
-                const int slot = i / 6, w = i - slot * 6;
-                const int row = RP == R ? slot : (slot / RP) * R + slot % RP;
-                const bool real = row < qLen && (RP == R || slot % RP < R);
-                uint32_t v = 0;
-                if (real) v = *reinterpret_cast<const uint32_t *>(L.q_prof + ((int64_t) jobA.q_start + (int64_t) row * jobA.q_step) * 32 + w * 4);
-#pragma unroll
-                for (int k = 0; k < 4; k++) if (4 * w + k < 22) prof[(4 * w + k) * ROWS + slot] = (int16_t) (int8_t) (v >> (8 * k));
+            const uint32_t count = min((uint32_t) (2 * GPB), wEnd - w0);
+            if constexpr (RF < R) {
+                // q_len is the wave's (one query per wave): a scalar load and a scalar branch
+                if (L.fine && !L.q_prof && L.jobs[L.order[w0]].q_len <= (uint32_t) (G * RF)) { swp_wave<RF, RP, G>(L, smem, w0, count, go2, ge2); continue; }
             }
-        } else {
-        for (int slot = (int) threadIdx.x; slot < ROWS; slot += 64) {
-            const int row = RP == R ? slot : (slot / RP) * R + slot % RP;    // lane-major: lane * R + r
-            const bool real = row < qLen && (RP == R || slot % RP < R);
-            const int64_t qi = (int64_t) jobA.q_start + (int64_t) (real ? row : 0) * jobA.q_step;
-            sQ[slot] = real ? L.q_res[qi] : (uint8_t) 255;
-            sB[slot] = real ? L.q_bias8[qi] : (int8_t) 0;
+            swp_wave<R, RP, G>(L, smem, w0, count, go2, ge2);
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int idx = (int) threadIdx.x; idx < 22 * ROWS; idx += 64) {
-            const int t = idx / ROWS, slot = idx - t * ROWS;
-            const uint32_t qc = sQ[slot];
-            prof[idx] = (t < 21 && qc != 255u) ? (int16_t) ((int) sMat[t * 21 + (int) qc] + (int) sB[slot]) : (int16_t) 0;
-        }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-
-        pk16 H[R], E[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) { H[r] = zero2; E[r] = zero2; }
-        pk16 best = zero2, hupPrev = zero2;
-        int roseA = 0, roseB = 0;                                  // first step of the block of 16 in which this lane's running maximum last rose
-        // what travels with a column is not the two residues but the byte offsets of their profile rows (residue * ROWS * 2, code 21 =
-        // "no column": an all-zero row), packed in one dword and prepared when the column is fetched -- nothing per step
-        constexpr uint32_t ROWB = (uint32_t) ROWS * 2u, NOCOL = 21u * ROWB | (21u * ROWB) << 16;
-        uint32_t outH = 0, outF = 0, outRes = NOCOL;              // handed to lane+1: H of the last row, F, the two profile-row offsets
-        const int tMax = max(tLenA, tLenB);
-        // whole blocks of 16 steps (the steps past the last column see all-zero profile rows, which cannot raise the maximum): the
-        // block is unrolled, so the lane-to-lane hand-over needs no register copies and no loop control
-        const int steps = tMax > 0 ? (tMax + G - 1 + 15) & ~15 : 0;
-        const int laneRow = lane & 15;                             // position in the DPP row (both rows of a 32-lane group fetch the same residues)
-        const int lastA = max(tLenA - 1, 0), lastB = max(tLenB - 1, 0);
-        const int64_t baseA = (int64_t) jobA.t_start, baseB = (int64_t) jobB.t_start, stepA = jobA.t_step, stepB = jobB.t_step;
-        const auto fetch = [&](int col) -> uint32_t {
-            const uint32_t ra = col < tLenA ? (uint32_t) L.t_res[baseA + (int64_t) min(col, lastA) * stepA] : 21u;
-            const uint32_t rb = col < tLenB ? (uint32_t) L.t_res[baseB + (int64_t) min(col, lastB) * stepB] : 21u;
-            return ra * ROWB | (rb * ROWB) << 16;
-        };
-        const char *profLane = reinterpret_cast<const char *>(prof + lane * RP);
-        // the residues of a block of 16 steps are fetched three blocks ahead: the loads have ~3 x 16 steps to land, which also covers the
-        // memory latency of a chip whose HBM the prefilter of the other stream keeps saturated
-        uint32_t tq0 = fetch(laneRow), tq1 = fetch(16 + laneRow), tq2 = fetch(32 + laneRow);
-        for (int s0 = 0; s0 < steps; s0 += 16) {
-            uint32_t tcur = tq0;
-            tq0 = tq1; tq1 = tq2;
-            tq2 = fetch(s0 + 48 + laneRow);
-            const uint32_t bestIn = pk_bits(best);
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                const uint32_t top = tcur;
-                tcur = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) tcur, 0x12F /* row_ror:15 */, 0xf, 0xf, false);
-                const pk16 hup = pk_from(shift_up_zero<G>(outH, lane));
-                pk16 F = pk_from(shift_up_zero<G>(outF, lane));
-                const uint32_t tres = shift_up<G>(top, outRes, lane);
-                const int16_t *pa = reinterpret_cast<const int16_t *>(profLane + (tres & 0xFFFFu)), *pb = reinterpret_cast<const int16_t *>(profLane + (tres >> 16));
-                uint32_t wa[RP / 2], wb[RP / 2];                   // R int16 scores per target, two per dword
-                if constexpr (RP % 4 == 0) {
-                    // a lane's RP scores are RP * 2 bytes at a multiple of 8: read as 64-bit words.  As dwords (ds_read2_b32) the lanes of a group sit on
-                    // every second bank and two groups share a cycle: 3.0 conflict cycles per active LDS cycle in the 48- / 64-row tiles
-                    // (profiles/r06_contention.txt)
-                    const uint64_t *qa = reinterpret_cast<const uint64_t *>(__builtin_assume_aligned(pa, 8)), *qb = reinterpret_cast<const uint64_t *>(__builtin_assume_aligned(pb, 8));
-#pragma unroll
-                    for (int k = 0; k < RP / 4; k++) {
-                        const uint64_t xa = qa[k], xb = qb[k];
-                        wa[2 * k] = (uint32_t) xa; wa[2 * k + 1] = (uint32_t) (xa >> 32); wb[2 * k] = (uint32_t) xb; wb[2 * k + 1] = (uint32_t) (xb >> 32);
-                    }
-                } else {
-#pragma unroll
-                for (int k = 0; k < RP / 2; k++) { wa[k] = reinterpret_cast<const uint32_t *>(pa)[k]; wb[k] = reinterpret_cast<const uint32_t *>(pb)[k]; }
-                }
-                pk16 dsave = hupPrev;
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    // (score of target A, score of target B) for row r: one byte permute
-                    const pk16 sc = pk_from(__builtin_amdgcn_perm(wb[r / 2], wa[r / 2], (r & 1) ? 0x07060302u : 0x05040100u));
-                    const pk16 d = SAT ? __builtin_elementwise_add_sat(dsave, sc) : dsave + sc;
-                    dsave = H[r];
-                    const pk16 h = pk_max(pk_max(d, E[r]), F);         // E, F >= 0 (clamped subtractions) keep H non-negative
-                    best = pk_max(best, h);
-                    const pk16 ho = pk_subs0(h, go2);
-                    E[r] = pk_max(pk_subs0(E[r], ge2), ho);
-                    F = pk_max(pk_subs0(F, ge2), ho);
-                    H[r] = h;
-                }
-                hupPrev = hup;
-                outH = pk_bits(H[R - 1]);
-                outF = pk_bits(F);
-                outRes = tres;
-            }
-            const uint32_t rose = pk_bits(best) ^ bestIn;
-            if (rose & 0xFFFFu) roseA = s0;
-            if (rose >> 16) roseB = s0;
-        }
-        // group reduction of the two maxima
-        uint32_t b = pk_bits(best);
-#pragma unroll
-        for (int m = G / 2; m >= 1; m >>= 1) b = pk_bits(pk_max(pk_from(b), pk_from((uint32_t) __shfl_xor((int) b, m, G))));
-        // ... and a bound for the position pass: a lane whose rows hold the maximum reached it in the block of steps in which its running
-        // maximum last rose, i.e. in a column <= that block's last step - lane; the first column that reaches the maximum (what the position
-        // pass reports) is not beyond the smallest such bound, so the position pass may stop there (the columns behind it cannot change its answer)
-        uint32_t cA = (pk_bits(best) & 0xFFFFu) == (b & 0xFFFFu) ? (uint32_t) max(roseA + 15 - lane, 0) : 0x7FFFFFFFu;
-        uint32_t cB = (pk_bits(best) >> 16) == (b >> 16) ? (uint32_t) max(roseB + 15 - lane, 0) : 0x7FFFFFFFu;
-#pragma unroll
-        for (int m = G / 2; m >= 1; m >>= 1) {
-            cA = min(cA, (uint32_t) __shfl_xor((int) cA, m, G));
-            cB = min(cB, (uint32_t) __shfl_xor((int) cB, m, G));
-        }
-        if (lane == 0) {
-            SwOut o;
-            o.end_row = -1; o.pad = 0;                              // end_col: not the end cell's column but a bound for it (gate_emit_kernel cuts the position job there)
-            if (haveA) { o.score = (int32_t) (int16_t) (b & 0xFFFFu); o.end_col = (int32_t) min(cA, (uint32_t) lastA); L.out[jobA.slot] = o; }
-            if (haveB) { o.score = (int32_t) (int16_t) (b >> 16); o.end_col = (int32_t) min(cB, (uint32_t) lastB); L.out[jobB.slot] = o; }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        }   // rounds of the wave
     }
 }
 
